@@ -94,7 +94,11 @@ def main():
                     "groups as the device memory allows (dist.ShardGrid.best_shape); Nx1 = row shards only")
     ap.add_argument("--share", default=None, metavar="RxG", help="N = 1 experiment: time one rank's share of an R x G job instead of the whole workload")
     ap.add_argument("--bucket", type=int, default=4, help="steps per collective of the bucketed side measurement (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the counters of the headline's last timed step to DIR/*.npy "
+                    "(float64), to compare two builds output for output on the same seeded inputs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     import faulthandler
     faulthandler.enable()           # a fatal signal leaves every thread's Python stack on stderr (the driver keeps stderr)
     t_main = time.time()
@@ -262,6 +266,15 @@ def main():
     if world > 1:
         dist.all_reduce(cs, op=dist.ReduceOp.SUM)
     checksum = [int(x) for x in cs.tolist()]
+    if a.dump_outputs:
+        # the whole [n_cand][3] result of the last timed step: every window group's slice (reduced over its row group), in window order
+        parts = [(gi, gpu_counters)] if ri == 0 else []
+        if world > 1:
+            got = [None] * world
+            dist.all_gather_object(got, parts)
+            parts = [p for ps in got for p in ps]
+        if rank == 0:
+            dump_outputs(a.dump_outputs, np.concatenate([c for _, c in sorted(parts, key=lambda p: p[0])]))
 
     # what the communicator itself says (N > 1): the ranks RCCL saw, through a communicator of the library's own
     comm_info = None
@@ -541,6 +554,23 @@ def emit(res):
                 pass
     print("bench_detail: " + detail, flush=True)
     print(headline(res), flush=True)
+
+
+DUMP_LIMIT = 64 << 20        # bytes of --dump-outputs in all
+
+
+def dump_outputs(d, counters):
+    """--dump-outputs: the counters of every candidate as DIR/coverage_counters.npy, float64 [n][3] (perfect, F_mis_cover, R_mis_cover:
+    mprime.h section 4; counts < 2^53 are exact).  Above DUMP_LIMIT a fixed, seeded sample of the candidates is written instead, and
+    DIR/coverage_counters_index.npy says which ones."""
+    os.makedirs(d, exist_ok=True)
+    out = counters.astype(np.float64)
+    keep = DUMP_LIMIT // 2 // out[0].nbytes
+    if len(out) > keep:
+        idx = np.sort(np.random.default_rng(0).choice(len(out), size=keep, replace=False))
+        np.save(os.path.join(d, "coverage_counters_index.npy"), idx.astype(np.float64))
+        out = out[idx]
+    np.save(os.path.join(d, "coverage_counters.npy"), out)
 
 
 def supervise(cmd, env=None, out=None, attempts=2):

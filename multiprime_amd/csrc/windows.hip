@@ -172,8 +172,10 @@ __global__ __launch_bounds__(kBlock) void repair_kernel(const MsaArgs M, int p0,
         for (int i = 0; i < 4; i++) ex[idx].q[i] = i < WordTraits<W>::kNibWords ? buf.q[i < WordTraits<W>::kNibWords ? i : 0] : 0ull;
         b0 = 0; b1 = 0; g = WordTraits<W>::kSkip | kmask;
     } else if (rc == 2) {
+        // the first short pair in the oracle's order (window, then row), whatever order the lanes run in: err[2..3] keep the
+        // largest ~(w << 32 | r)
         atomicMax(err, 1);
-        err[1] = w; err[2] = r;
+        atomicMax(reinterpret_cast<unsigned long long *>(err + 2), ~(((unsigned long long)w << 32) | (unsigned)r));
         b0 = 0; b1 = 0; g = WordTraits<W>::kSkip | kmask;
     }
     words[3 * (size_t)e] = b0; words[3 * (size_t)e + 1] = b1; words[3 * (size_t)e + 2] = g;
@@ -345,8 +347,12 @@ int mp_build_windows(mp_ctx *c, int32_t p0, int32_t n_win, int32_t k, int32_t v,
         dev_free(c, &d_wins, (size_t)tot);
         lap("build_windows: scratch released");
         if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "mp_build_windows: %s", hipGetErrorString(e));
-        if (errv[0])
-            return fail(c, MP_ERR_SHORT_WINDOW, "row %d has fewer than %d residues at window %d", errv[2], k, p0 + errv[1]);
+        if (errv[0]) {
+            unsigned long long first;                                           // repair_kernel: ~(window << 32 | row)
+            memcpy(&first, errv + 2, sizeof(first));
+            first = ~first;
+            return fail(c, MP_ERR_SHORT_WINDOW, "row %d has fewer than %d residues at window %d", (int)(first & 0xffffffffu), k, p0 + (int)(first >> 32));
+        }
         // the records (40 bytes each) stay on the device until someone asks: ex_fetch() — the caller's helper thread (mp_get_exceptions) or
         // the histogram's host part, both beside the histogram kernels instead of in front of them
         if (cnt && !c->ex_stream) HIPCK(c, hipStreamCreateWithFlags(&c->ex_stream, hipStreamNonBlocking));     // (created on the calling thread)

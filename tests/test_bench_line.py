@@ -93,3 +93,20 @@ def test_supervisor_passes_a_finished_child_through_and_retries_an_early_death(t
     rc = bench.supervise(_fake_child(tmp_path, f"p = {str(marker)!r}\nif not os.path.exists(p):\n    open(p, 'w').close(); os.kill(os.getpid(), signal.SIGSEGV)\n"
                                                "print(json.dumps({'metric': 'm', 'value': 3.0}))\n"), out=out)
     assert rc == 0 and json.loads(out.getvalue().splitlines()[-1])["value"] == 3.0
+
+
+def test_dump_outputs_writes_float64_counters_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    bench = _bench()
+    counters = np.random.default_rng(3).integers(0, 1 << 40, size=(1000, 3), dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "all"), counters)
+    got = np.load(tmp_path / "all" / "coverage_counters.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), counters)
+    assert not (tmp_path / "all" / "coverage_counters_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100 * 2 * 24)                  # room for 100 candidates and their indices
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), counters)
+    idx, got = np.load(tmp_path / "s1" / "coverage_counters_index.npy"), np.load(tmp_path / "s1" / "coverage_counters.npy")
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and np.array_equal(got.astype(np.int64), counters[idx.astype(np.int64)])
+    assert idx.nbytes + got.nbytes <= bench.DUMP_LIMIT
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "coverage_counters_index.npy"))     # the same sample every run

@@ -1,19 +1,21 @@
 """SURVEY §8c end-to-end known answer: this build's core output, fed through the REFERENCE's own
 pairing script (get_multiPrime.py, unmodified) and then through this build's get_Maxprimerset,
-must select the reference's final primer pair.  Needs /root/reference (authoring container only)."""
-import os
-import subprocess
-import sys
-import types
+must select the reference's final primer pair.
 
-import pytest
+The reference's pairing stage is not run here.  Its candidate file for this core output and these
+flags is the one recorded in tests/golden/pairing.json.gz (tests/golden/make_golden_pairing.py:
+fixture cluster0_v1, flag set `yaml`); the script writes the same bytes with the cluster's own
+.tfa as -r.  The core step is run here and must reproduce the reference core's files that recording
+was made from."""
+import types
 
 from conftest import golden_input, load_gz_json
 from multiprime_amd import maxset
 from multiprime_amd.core import NN_degenerate
+from test_core_golden import check_outputs
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present")
+PAIRING_FLAGS = ["-f", "0.7", "-s", "150,1200", "-g", "0.2,0.7", "-e", "4", "-d", "4", "-a",
+                 "TCTTTCCCTACACGACGCTCTTCCGATCT,TGGAGTTCAGACGTGTGCTCTTCCGATCT", "-m", "0"]
 
 
 def test_core_to_reference_pairing_to_primer_set(oracle_lib, tmp_path):
@@ -25,12 +27,11 @@ def test_core_to_reference_pairing_to_primer_set(oracle_lib, tmp_path):
     NN_degenerate(seq_file=str(inp), primer_length=fl["l"], coverage=fl["f"], number_of_dege_bases=fl["n"],
                   score_of_dege_bases=fl["d"], raw_entropy_threshold=fl["e"], product_len=fl["s"], position=fl["c"],
                   variation=fl["v"], distance=fl["a"], GC=fl["g"], nproc=1, outfile=str(out), library=oracle_lib).run()
-    tfa = os.path.join(REF, "test_data", "results", "Clusters_fa", "Cluster_0_20727.tfa")
+    check_outputs("cluster0_v1", out)                                      # TSV and both JSON side files the pairing script reads
+    gold = load_gz_json("pairing.json.gz")
+    assert gold["flags"]["yaml"] == PAIRING_FLAGS
     cand = tmp_path / "Cluster_0_20727.candidate.primers.txt"
-    subprocess.check_call([sys.executable, os.path.join(REF, "scripts", "get_multiPrime.py"), "-i", str(out), "-r", tfa,
-                           "-f", "0.7", "-s", "150,1200", "-g", "0.2,0.7", "-e", "4", "-d", "4", "-a",
-                           "TCTTTCCCTACACGACGCTCTTCCGATCT,TGGAGTTCAGACGTGTGCTCTTCCGATCT", "-m", "0", "-o", str(cand), "-p", "1"],
-                          stdout=subprocess.DEVNULL, cwd=str(tmp_path))
+    cand.write_text(gold["results"]["cluster0_v1"]["yaml"]["txt"].replace("<OUT>", str(cand)))
     fields = [x for x in cand.read_text().strip().split("\t") if x]
     assert (len(fields) - 1) // 5 == 2749
     assert fields[1:6] == ["RRTCAGATGCACCYATTG", "CCCAKRTCYTCAGCATTT", "566:51.59:0.968", "484", "888:1453"]
