@@ -90,6 +90,13 @@ SYMBOLS = [
     ("mp_device_bytes", C.c_int, [_p, C.POINTER(C.c_int64)]),
 ]
 COMM_ID_BYTES = 128
+# include/mprime_offtarget.h: the off-target screen on the device (csrc/offtarget.hip) — exported by libmprime_hip.so only; bound where
+# a library has them (the oracle serves mprime.h alone: the checker of these calls is the host path of validate.py)
+OFFTARGET_SYMBOLS = [
+    ("mp_offtarget_resident", C.c_int, [_p, C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
+    ("mp_amplicon_join", C.c_int, [_p, C.c_int64, _p, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
+    ("mp_offtarget_stats", C.c_int, [_p, _p, _p]),
+]
 
 
 def prefer_staged_copies():
@@ -177,6 +184,13 @@ class Library:
             fn.restype = res
             fn.argtypes = args
         self.backend = self.dll.mp_backend_name().decode()
+        self.offtarget = all(hasattr(self.dll, name) for name, _, _ in OFFTARGET_SYMBOLS)
+        if self.backend == "hip" and not self.offtarget:
+            raise MprimeError(-2, f"{path} lacks the off-target entry points of include/mprime_offtarget.h: rebuild it")
+        for name, res, args in OFFTARGET_SYMBOLS if self.offtarget else ():
+            fn = getattr(self.dll, name)
+            fn.restype = res
+            fn.argtypes = args
         if implicit and self.backend != "hip":
             raise MprimeError(-2, f"{path} reports backend {self.backend!r}, not 'hip': the product runs on libmprime_hip.so only "
                                   "(MPRIME_LIBRARY may name another build of it, not the CPU checker)")
@@ -626,6 +640,51 @@ class Context:
                 h = hits[: n.value]
                 return h[np.lexsort((h[:, 3], h[:, 2], h[:, 1], h[:, 0]))] if len(h) else h
             cap = int(n.value)
+
+    # include/mprime_offtarget.h
+    def _need_offtarget(self):
+        if not self.lib.offtarget:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_offtarget.h (libmprime_hip.so does)")
+
+    def offtarget_resident(self, pat_codes, pat_off, read_primer, max_mismatch, term: int, size_lo: int, size_hi: int, cap: int = 1 << 20) -> np.ndarray:
+        """Products [n][6] = (sequence, start, stop, forward primer id, reverse primer id, length) of the off-target screen of the stored
+        database, in the order of the report.  Patterns are the reads in ascending read order; max_mismatch per read (or one for all).
+        A result larger than `cap` is fetched again with the exact size: the library kept it, nothing is scanned twice."""
+        self._need_offtarget()
+        pat_codes = np.ascontiguousarray(pat_codes, dtype=np.uint8)
+        pat_off = np.ascontiguousarray(pat_off, dtype=np.int32)
+        n_pat = len(pat_off) - 1
+        read_primer = np.ascontiguousarray(read_primer, dtype=np.int32)
+        mm = np.ascontiguousarray(np.broadcast_to(np.asarray(max_mismatch, np.int32), (n_pat,)), dtype=np.int32)
+        while True:
+            out = np.empty((max(cap, 1), 6), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_offtarget_resident(self.h, n_pat, _ptr(pat_codes), _ptr(pat_off), _ptr(read_primer), _ptr(mm), int(term),
+                                                  int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
+            if n.value <= cap:
+                return out[: n.value]
+            cap = int(n.value)
+
+    def amplicon_join(self, sites, size_lo: int, size_hi: int, cap: int = 1 << 20) -> np.ndarray:
+        """The join alone: sites [n][4] = (strand, row, position, primer id), strictly ascending in (strand, row, position); products
+        [n][6] as offtarget_resident, rows ascending."""
+        self._need_offtarget()
+        sites = np.ascontiguousarray(sites, dtype=np.int32).reshape(-1, 4)
+        while True:
+            out = np.empty((max(cap, 1), 6), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_amplicon_join(self.h, len(sites), _ptr(sites), int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
+            if n.value <= cap:
+                return out[: n.value]
+            cap = int(n.value)
+
+    def offtarget_stats(self):
+        """Of the last offtarget_resident / amplicon_join: ({scan, reduce, join, call}_ms, {hits, sites and sequences per strand, products})."""
+        self._need_offtarget()
+        ms, counts = np.zeros(4, np.float64), np.zeros(7, np.int64)
+        self._ck(self.d.mp_offtarget_stats(self.h, _ptr(ms), _ptr(counts)))
+        return (dict(zip(("scan_ms", "reduce_ms", "join_ms", "call_ms"), ms.tolist())),
+                dict(zip(("hits", "forward_sites", "reverse_sites", "products", "forward_genes", "reverse_genes", "both_genes"), counts.tolist())))
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

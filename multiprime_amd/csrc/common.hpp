@@ -265,6 +265,13 @@ struct mp_ctx {
     int32_t sq_n = 0;
     size_t sq_total = 0, sq_words = 0;
     std::vector<int64_t> sq_roff_host;
+    // the off-target screen (offtarget.hip): the products of the last mp_offtarget_resident, kept for a repeat of the call with a larger
+    // cap (ot_key: its arguments; free_seq drops them with the store), and the stage times / counts of the last call (mp_offtarget_stats)
+    int32_t *ot_out = nullptr;
+    int64_t ot_n = 0;
+    std::vector<uint8_t> ot_key;
+    double ot_ms[4] = {0, 0, 0, 0};
+    int64_t ot_counts[7] = {0, 0, 0, 0, 0, 0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run

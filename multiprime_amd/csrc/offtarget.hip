@@ -1,0 +1,614 @@
+// offtarget.hip — part of libmprime_hip.so: hand-written HIP (gfx950 / MI355X, wave64) behind include/mprime_offtarget.h.
+// The off-target screen of scripts/primer_specificity.py without the hits ever leaving the device:
+//
+//   scan     kmm_kernel (kmm.hpp: mp_kmm_scan's rule and pattern table) over the resident store, one launch per mismatch budget.  Its
+//            sink folds every hit into a SITE MAP — one uint32 per (strand, base of the store) holding 1 + the largest read index that
+//            hit there (atomicMax) — and keeps, per sequence, the smallest read index with a forward hit (a wave minimum, one atomicMin
+//            per wave).  The reduction IS the scan: there is no hit list to size, to overflow or to sort.
+//   reduce   stream compaction of the map (count per chunk, exclusive scan, stable write): the sites of both strands, ascending in
+//            (strand, sequence, position) because the map is laid out that way, each with its read mapped to its primer id; then the
+//            first site of every (strand, sequence) by binary search.
+//   join     validate.amplicons() per sequence: one thread per forward site counts its stops (binary searches in the sequence's reverse
+//            sites), marks the whole-sequence reject and the first start without a stop (atomicMin per sequence); an exclusive scan of
+//            the counts; the sequences' order (smallest read with a forward hit, sequence) on the host over the per-sequence totals —
+//            O(sequences), no hit or site crosses the bus —; then one thread per start writes its products.
+//
+// mp_amplicon_join runs the join on explicit sites (position key row << 32 | position instead of the store's offsets).
+#include "common.hpp"
+#include "kmm.hpp"
+#include "../../include/mprime_offtarget.h"
+
+#include <tuple>
+
+using namespace mp;
+
+namespace {
+
+constexpr int kChunk = kBlock * 16;              // map entries per workgroup of the compaction
+constexpr int kScanTile = kBlock * 8;            // elements per workgroup of the exclusive scan
+constexpr int kOtCounts = 7;                     // mp_offtarget_stats counts
+
+// ---- the scan's sink ---------------------------------------------------------------------------------------------------------------
+struct OtSites {
+    struct State { int mn; unsigned hits; };
+    uint32_t *map;                    // [2][n_bases]: forward half, reverse half
+    const int64_t *roff;              // the store's byte offsets
+    long long n_bases;
+    int32_t *row_min;                 // [n_rows] smallest read with a forward hit (0x7fffffff: none)
+    unsigned long long *n_hits;
+    __device__ State begin() const { return {0x7fffffff, 0u}; }
+    __device__ void hit(State &st, int row, long long p, int id, int strand) const {
+        atomicMax(map + (strand ? n_bases : 0) + roff[row] + p, (uint32_t)id + 1u);
+        if (!strand) st.mn = min(st.mn, id);
+        st.hits++;
+    }
+    __device__ void end(State &st, int row) const {     // the whole wave arrives here (one row per workgroup)
+        int mn = st.mn;
+        unsigned h = st.hits;
+        for (int o = 32; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); h += __shfl_xor(h, o); }
+        if (__lane_id() == 0) {
+            if (mn != 0x7fffffff) atomicMin(row_min + row, mn);
+            if (h) atomicAdd(n_hits, (unsigned long long)h);
+        }
+    }
+};
+
+// ---- block-wide helpers (kBlock = 256 threads = 4 waves) ------------------------------------------------------------------------------
+__device__ long long block_sum(long long v, long long *s_w) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if (__lane_id() == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// exclusive prefix of v over the block in thread order; *total = the block's sum
+__device__ long long block_exclusive(long long v, long long *s_w, long long *total) {
+    const int lane = __lane_id(), w = threadIdx.x >> 6;
+    long long x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    __syncthreads();
+    if (lane == 63) s_w[w] = x;
+    __syncthreads();
+    long long before = 0;
+    for (int i = 0; i < w; i++) before += s_w[i];
+    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return before + x - v;
+}
+
+// ---- exclusive scan of int64 (out[0..n]: out[n] = the total) ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void scan_tiles_kernel(const long long *__restrict__ in, long long n, long long *__restrict__ part) {
+    __shared__ long long s_w[4];
+    const long long i0 = (long long)blockIdx.x * kScanTile + threadIdx.x * 8;
+    long long v = 0;
+    for (int j = 0; j < 8; j++) if (i0 + j < n) v += in[i0 + j];
+    v = block_sum(v, s_w);
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// one tile of kScanTile elements from `start`, with `carry` in front; returns the tile's sum (every thread)
+__device__ long long scan_tile(const long long *in, long long *out, long long n, long long start, long long carry, long long *s_w) {
+    const long long i0 = start + threadIdx.x * 8;
+    long long e[8], v = 0;
+    for (int j = 0; j < 8; j++) { e[j] = i0 + j < n ? in[i0 + j] : 0; v += e[j]; }
+    long long total;
+    long long run = carry + block_exclusive(v, s_w, &total);
+    for (int j = 0; j < 8; j++) {
+        if (i0 + j < n) out[i0 + j] = run;
+        run += e[j];
+    }
+    return total;
+}
+
+// the tile sums, scanned in place by one workgroup; the grand total to *total_out
+__global__ __launch_bounds__(kBlock) void scan_parts_kernel(long long *part, long long n_part, long long *__restrict__ total_out) {
+    __shared__ long long s_w[4];
+    long long carry = 0;
+    for (long long t = 0; t < n_part; t += kScanTile) carry += scan_tile(part, part, n_part, t, carry, s_w);
+    if (threadIdx.x == 0) *total_out = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void scan_apply_kernel(const long long *__restrict__ in, long long n, const long long *__restrict__ part,
+                                                            long long *__restrict__ out) {
+    __shared__ long long s_w[4];
+    (void)scan_tile(in, out, n, (long long)blockIdx.x * kScanTile, part[blockIdx.x], s_w);
+}
+
+// ---- reduce: compaction of the site map --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void map_count_kernel(const uint32_t *__restrict__ map, long long n2, long long *__restrict__ cnt) {
+    __shared__ long long s_w[4];
+    const long long c0 = (long long)blockIdx.x * kChunk;
+    long long v = 0;
+    for (int r = 0; r < kChunk / kBlock; r++) {
+        const long long i = c0 + r * kBlock + threadIdx.x;
+        v += i < n2 && map[i] != 0;
+    }
+    v = block_sum(v, s_w);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = v;
+}
+
+// the sites of one chunk in map order from base[chunk]: key = map index, primer = read_primer[read]
+__global__ __launch_bounds__(kBlock) void map_write_kernel(const uint32_t *__restrict__ map, long long n2, const long long *__restrict__ base,
+                                                           const int32_t *__restrict__ read_primer, long long *__restrict__ key,
+                                                           int32_t *__restrict__ primer) {
+    __shared__ long long s_w[4];
+    const long long c0 = (long long)blockIdx.x * kChunk;
+    long long run = base[blockIdx.x];
+    for (int r = 0; r < kChunk / kBlock; r++) {
+        const long long i = c0 + r * kBlock + threadIdx.x;
+        const uint32_t m = i < n2 ? map[i] : 0u;
+        long long total;
+        const long long at = run + block_exclusive(m != 0, s_w, &total);
+        if (m) { key[at] = i; primer[at] = read_primer[m - 1]; }
+        run += total;
+    }
+}
+
+__device__ long long lower_bound(const long long *a, long long lo, long long hi, long long x) {     // first index in [lo, hi) with a[i] >= x
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// first site of every (strand, row): f_lo[r] / r_lo[r] for r = 0 .. n_rows (the last entry ends the strand)
+__global__ __launch_bounds__(kBlock) void site_rows_kernel(const long long *__restrict__ key, long long n_sites, const int64_t *__restrict__ roff,
+                                                           int n_rows, long long n_bases, long long *__restrict__ f_lo, long long *__restrict__ r_lo) {
+    const long long r = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (r > n_rows) return;
+    f_lo[r] = lower_bound(key, 0, n_sites, roff[r]);
+    r_lo[r] = lower_bound(key, 0, n_sites, n_bases + roff[r]);
+}
+
+// ---- join -------------------------------------------------------------------------------------------------------------------------------
+struct JoinArgs {
+    const long long *key;             // site keys: forward sites [0, n_fwd) hold the position key, reverse sites hold n_bases + it
+    const int32_t *primer;
+    const int64_t *roff;              // position key of a row's first base
+    int n_rows;
+    long long n_bases, n_fwd;
+    const long long *f_lo, *r_lo;
+    long long lo, hi;                 // the size range
+};
+
+__device__ int row_of(const JoinArgs &A, long long k) {      // the row whose range [roff[r], roff[r + 1]) holds k
+    int lo = 0, hi = A.n_rows;                                // last r with roff[r] <= k
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (A.roff[mid] <= k) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// per forward site: its row, its number of products before the per-row cuts, and the cuts (whole-row reject, first dead start)
+__global__ __launch_bounds__(kBlock) void join_count_kernel(JoinArgs A, int32_t *__restrict__ site_row, long long *__restrict__ cnt,
+                                                            int32_t *__restrict__ dead) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n_fwd) return;
+    const long long a = A.key[i];
+    const int row = row_of(A, a);
+    site_row[i] = row;
+    cnt[i] = 0;
+    const long long rlo = A.r_lo[row], rhi = A.r_lo[row + 1], flo = A.f_lo[row], fhi = A.f_lo[row + 1];
+    if (rlo == rhi) return;                                                   // no reverse site: not a gene of `both`
+    const long long t_first = A.key[rlo] - A.n_bases, t_last = A.key[rhi - 1] - A.n_bases;
+    if (t_first - A.key[fhi - 1] > A.hi || t_last - A.key[flo] < A.lo) return;  // the whole row gives nothing
+    const long long first = lower_bound(A.key, rlo, rhi, A.n_bases + a + A.lo);
+    const long long last = a + A.hi > t_last ? rhi - 1 : lower_bound(A.key, rlo, rhi, A.n_bases + a + A.hi) - 1;
+    if (first > last) { atomicMin(dead + row, (int32_t)(i - flo)); return; }  // this start and every later one of the row: nothing
+    // stop - start + 1 < hi  <=>  stop <= start + hi - 2; from `first` on stop >= start + lo, so the lower bound holds already
+    const long long end = lower_bound(A.key, first, rhi, A.n_bases + a + A.hi - 1);
+    cnt[i] = end - first;
+}
+
+__global__ __launch_bounds__(kBlock) void join_cut_kernel(JoinArgs A, const int32_t *__restrict__ site_row, const int32_t *__restrict__ dead,
+                                                          long long *__restrict__ cnt) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n_fwd) return;
+    const int row = site_row[i];
+    if (i - A.f_lo[row] >= dead[row]) cnt[i] = 0;
+}
+
+// products per row (off = the exclusive scan of the counts, n_fwd + 1 entries); rows with forward / reverse / both kinds of sites
+__global__ __launch_bounds__(kBlock) void join_rows_kernel(JoinArgs A, const long long *__restrict__ off, long long *__restrict__ total,
+                                                           unsigned long long *__restrict__ genes) {
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= A.n_rows) return;
+    total[r] = off[A.f_lo[r + 1]] - off[A.f_lo[r]];
+    const bool f = A.f_lo[r + 1] > A.f_lo[r], b = A.r_lo[r + 1] > A.r_lo[r];
+    if (f) atomicAdd(genes, 1ull);
+    if (b) atomicAdd(genes + 1, 1ull);
+    if (f && b) atomicAdd(genes + 2, 1ull);
+}
+
+__global__ __launch_bounds__(kBlock) void join_emit_kernel(JoinArgs A, const int32_t *__restrict__ site_row, const long long *__restrict__ off,
+                                                           const long long *__restrict__ row_base, int32_t *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n_fwd) return;
+    const long long n = off[i + 1] - off[i];
+    if (n == 0) return;
+    const int row = site_row[i];
+    const long long a = A.key[i], r0 = A.roff[row];
+    const long long first = lower_bound(A.key, A.r_lo[row], A.r_lo[row + 1], A.n_bases + a + A.lo);
+    int32_t *o = out + 6 * (row_base[row] + off[i] - off[A.f_lo[row]]);
+    for (long long j = 0; j < n; j++, o += 6) {
+        const long long b = A.key[first + j] - A.n_bases;
+        o[0] = row; o[1] = (int32_t)(a - r0); o[2] = (int32_t)(b - r0); o[3] = A.primer[i]; o[4] = A.primer[first + j]; o[5] = (int32_t)(b - a + 1);
+    }
+}
+
+inline unsigned grid(long long n, long long per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
+
+// exclusive scan of n int64 into out[0..n] (device arrays; `out` may not alias `in`)
+int scan_i64(mp_ctx *c, const long long *in, long long n, long long *out) {
+    const long long n_part = (n + kScanTile - 1) / kScanTile;
+    long long *part = nullptr;
+    int rc;
+    if ((rc = dev_alloc(c, &part, (size_t)n_part + 1))) return rc;
+    if (n_part) hipLaunchKernelGGL(scan_tiles_kernel, dim3(grid(n, kScanTile)), dim3(kBlock), 0, c->stream, in, n, part);
+    hipLaunchKernelGGL(scan_parts_kernel, dim3(1), dim3(kBlock), 0, c->stream, part, n_part, out + n);
+    if (n_part) hipLaunchKernelGGL(scan_apply_kernel, dim3(grid(n, kScanTile)), dim3(kBlock), 0, c->stream, in, n, (const long long *)part, out);
+    hipError_t e = hipGetLastError();
+    dev_free(c, &part, (size_t)n_part + 1);
+    if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "scan: %s", hipGetErrorString(e));
+    return MP_OK;
+}
+
+// Everything after the sites: sites [0, n_fwd) forward, [n_fwd, n_sites) reverse (key n_bases + position key), rows keyed by row_key
+// (int32 per row: the sequence order is ascending (row_key, row)).  Products into c->ot_out (c->ot_n of them).
+int join_device(mp_ctx *c, const long long *d_key, const int32_t *d_primer, long long n_sites, const int64_t *d_roff, int n_rows,
+                long long n_bases, const int32_t *d_row_key, int32_t size_lo, int32_t size_hi) {
+    long long *f_lo = nullptr, *r_lo = nullptr, *cnt = nullptr, *off = nullptr, *rtot = nullptr, *rbase = nullptr;
+    unsigned long long *genes = nullptr;
+    int32_t *site_row = nullptr, *dead = nullptr;
+    const size_t nr1 = (size_t)n_rows + 1;
+    long long n_fwd = 0;
+    int rc = MP_OK;
+    hipError_t e = hipSuccess;
+    auto cleanup = [&]() {
+        dev_free(c, &f_lo, nr1); dev_free(c, &r_lo, nr1); dev_free(c, &rtot, nr1); dev_free(c, &rbase, nr1); dev_free(c, &dead, nr1);
+        dev_free(c, &genes, 3);
+    };
+    if ((rc = dev_alloc(c, &f_lo, nr1)) || (rc = dev_alloc(c, &r_lo, nr1)) || (rc = dev_alloc(c, &rtot, nr1)) || (rc = dev_alloc(c, &rbase, nr1)) ||
+        (rc = dev_alloc(c, &dead, nr1)) || (rc = dev_alloc(c, &genes, 3))) { cleanup(); return rc; }
+    hipLaunchKernelGGL(site_rows_kernel, dim3(grid(n_rows + 1, kBlock)), dim3(kBlock), 0, c->stream, d_key, n_sites, d_roff, n_rows, n_bases, f_lo, r_lo);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_fwd, f_lo + n_rows, sizeof n_fwd, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget sites: %s", hipGetErrorString(e)); }
+    c->ot_counts[1] = n_fwd;
+    c->ot_counts[2] = n_sites - n_fwd;
+    JoinArgs A{d_key, d_primer, d_roff, n_rows, n_bases, n_fwd, f_lo, r_lo, size_lo, size_hi};
+    const size_t nf = (size_t)std::max<long long>(n_fwd, 1);
+    if ((rc = dev_alloc(c, &site_row, nf)) || (rc = dev_alloc(c, &cnt, nf)) || (rc = dev_alloc(c, &off, nf + 1))) {
+        dev_free(c, &site_row, nf); dev_free(c, &cnt, nf); dev_free(c, &off, nf + 1); cleanup(); return rc;
+    }
+    auto cleanup2 = [&]() { dev_free(c, &site_row, nf); dev_free(c, &cnt, nf); dev_free(c, &off, nf + 1); cleanup(); };
+    FillSeg segs[2] = {{dead, nr1 * 4, 0x7fffffffu}, {genes, 3 * sizeof(unsigned long long), 0u}};
+    if ((rc = fill_segments(c, segs, 2))) { cleanup2(); return rc; }
+    if (n_fwd) {
+        hipLaunchKernelGGL(join_count_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, site_row, cnt, dead);
+        hipLaunchKernelGGL(join_cut_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, (const int32_t *)site_row, (const int32_t *)dead, cnt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && (rc = scan_i64(c, cnt, n_fwd, off))) { cleanup2(); return rc; }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(join_rows_kernel, dim3(grid(n_rows, kBlock)), dim3(kBlock), 0, c->stream, A, (const long long *)off, rtot, genes);
+        e = hipGetLastError();
+    }
+    // the sequence order: per-row totals and keys to the host (O(rows)), sorted there, the bases back
+    std::vector<long long> h_tot((size_t)n_rows), h_base((size_t)n_rows, 0);
+    std::vector<int32_t> h_key((size_t)n_rows);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_tot.data(), rtot, sizeof(long long) * n_rows, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_key.data(), d_row_key, sizeof(int32_t) * n_rows, hipMemcpyDeviceToHost, c->stream);
+    unsigned long long h_genes[3] = {0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(h_genes, genes, sizeof h_genes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup2(); return fail(c, MP_ERR_DEVICE, "offtarget join: %s", hipGetErrorString(e)); }
+    for (int i = 0; i < 3; i++) c->ot_counts[4 + i] = (int64_t)h_genes[i];
+    std::vector<std::pair<int32_t, int32_t>> order;
+    for (int r = 0; r < n_rows; r++) if (h_tot[(size_t)r]) order.push_back({h_key[(size_t)r], r});
+    std::sort(order.begin(), order.end());
+    long long total = 0;
+    for (auto &kr : order) { h_base[(size_t)kr.second] = total; total += h_tot[(size_t)kr.second]; }
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
+    c->ot_n = 0;
+    if ((rc = dev_alloc(c, &c->ot_out, (size_t)std::max<long long>(total, 1) * 6))) { cleanup2(); return rc; }
+    c->ot_n = total;
+    if (total) {
+        e = hipMemcpyAsync(rbase, h_base.data(), sizeof(long long) * n_rows, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(join_emit_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, (const int32_t *)site_row,
+                               (const long long *)off, (const long long *)rbase, c->ot_out);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);       // (h_base leaves scope)
+    }
+    cleanup2();
+    if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "offtarget emit: %s", hipGetErrorString(e));
+    c->ot_counts[3] = total;
+    return MP_OK;
+}
+
+// the first min(cap, ot_n) kept products to the caller
+int copy_out(mp_ctx *c, int64_t cap, int32_t *out, int64_t *n_out) {
+    *n_out = c->ot_n;
+    const long long n = std::min<long long>(cap, c->ot_n);
+    if (n > 0) {
+        HIPCK(c, hipMemcpyAsync(out, c->ot_out, sizeof(int32_t) * 6 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+    }
+    return MP_OK;
+}
+
+template <class T> void put(std::vector<uint8_t> &k, const T *p, size_t n) {
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
+    k.insert(k.end(), b, b + sizeof(T) * n);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+}  // namespace
+
+extern "C" {
+
+int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
+                          const int32_t *max_mm, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {
+    if (!c) return MP_ERR_ARG;
+    if (n_pat < 0 || !n_out || cap < 0 || (cap && !out) || (n_pat && (!pat_codes || !pat_off || !read_primer || !max_mm)) || term < 0)
+        return fail(c, MP_ERR_ARG, "mp_offtarget_resident: bad arguments");
+    HIPCK(c, hipSetDevice(c->dev));
+    const auto t0 = std::chrono::steady_clock::now();
+    *n_out = 0;
+    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
+    for (int32_t i = 0; i < n_pat; i++) {
+        const int len = pat_off[i + 1] - pat_off[i];
+        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
+        for (int j = 0; j < len; j++) {
+            const uint8_t m = pat_codes[pat_off[i] + j];
+            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
+        }
+        if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative mismatch budget", i);
+    }
+    if (c->sq_n == 0 || n_pat == 0) {
+        for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+        dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
+        c->ot_n = 0;
+        c->ot_key.clear();
+        return MP_OK;
+    }
+    // a repeat of the last call (a larger cap after *n_out > cap): its products are still on the device
+    std::vector<uint8_t> key;
+    const int32_t head[4] = {n_pat, term, size_lo, size_hi};
+    put(key, head, 4);
+    put(key, pat_off, (size_t)n_pat + 1);
+    put(key, pat_codes + pat_off[0], (size_t)(pat_off[n_pat] - pat_off[0]));
+    put(key, read_primer, (size_t)n_pat);
+    put(key, max_mm, (size_t)n_pat);
+    if (!c->ot_key.empty() && key == c->ot_key) {
+        int rc = copy_out(c, cap, out, n_out);
+        c->ot_ms[3] = ms_since(t0);
+        return rc;
+    }
+    c->ot_key.clear();
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+    const long long n_bases = (long long)c->sq_total, n2 = 2 * n_bases;
+    const int n_rows = c->sq_n;
+    // the workgroups of the scan: (row, segment) as in mp_kmm_scan
+    std::vector<int32_t> blk_row, blk_seg;
+    for (int32_t r = 0; r < n_rows; r++) {
+        const int64_t len = c->sq_roff_host[(size_t)r + 1] - c->sq_roff_host[(size_t)r];
+        for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
+    }
+    const size_t nb = std::max<size_t>(blk_row.size(), 1);
+    // one pattern table per mismatch budget (ids: the global read index)
+    std::vector<int32_t> budgets(max_mm, max_mm + n_pat);
+    std::sort(budgets.begin(), budgets.end());
+    budgets.erase(std::unique(budgets.begin(), budgets.end()), budgets.end());
+    struct Table { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; };
+    std::vector<Table> tables;
+    for (int32_t b : budgets) {
+        std::vector<uint8_t> codes;
+        std::vector<int32_t> off{0}, ids;
+        int longest = 0;
+        for (int32_t i = 0; i < n_pat; i++) {
+            if (max_mm[i] != b) continue;
+            codes.insert(codes.end(), pat_codes + pat_off[i], pat_codes + pat_off[i + 1]);
+            off.push_back((int32_t)codes.size());
+            ids.push_back(i);
+            longest = std::max(longest, pat_off[i + 1] - pat_off[i]);
+        }
+        Table T{b, longest > 32, {}, 0};
+        auto fill = [&](auto &pats) {
+            kmm_patterns(off.size() - 1, codes.data(), off.data(), term, pats);
+            for (auto &P : pats) P.id = ids[(size_t)P.id];
+            T.n = (int)pats.size();
+            put(T.bytes, pats.data(), pats.size());
+        };
+        if (T.two) { std::vector<KmmPat<2>> p; fill(p); } else { std::vector<KmmPat<1>> p; fill(p); }
+        tables.push_back(std::move(T));
+    }
+    size_t pat_bytes = 1;
+    for (auto &T : tables) pat_bytes = std::max(pat_bytes, T.bytes.size());
+
+    uint32_t *map = nullptr;
+    int32_t *row_min = nullptr, *d_brow = nullptr, *d_bseg = nullptr, *d_rp = nullptr, *primer = nullptr;
+    uint8_t *d_pats = nullptr;
+    unsigned long long *d_hits = nullptr;
+    long long *ccnt = nullptr, *cbase = nullptr, *skey = nullptr;
+    const long long n_chunks = (n2 + kChunk - 1) / kChunk;
+    long long n_sites = 0;
+    size_t ns = 1;
+    auto cleanup = [&]() {
+        dev_free(c, &map, (size_t)n2); dev_free(c, &row_min, (size_t)n_rows); dev_free(c, &d_brow, nb); dev_free(c, &d_bseg, nb);
+        dev_free(c, &d_rp, (size_t)n_pat); dev_free(c, &d_pats, pat_bytes); dev_free(c, &d_hits, 1); dev_free(c, &ccnt, (size_t)n_chunks);
+        dev_free(c, &cbase, (size_t)n_chunks + 1); dev_free(c, &skey, ns); dev_free(c, &primer, ns);
+    };
+    int rc;
+    if ((rc = dev_alloc(c, &map, (size_t)n2)) || (rc = dev_alloc(c, &row_min, (size_t)n_rows)) || (rc = dev_alloc(c, &d_brow, nb)) ||
+        (rc = dev_alloc(c, &d_bseg, nb)) || (rc = dev_alloc(c, &d_rp, (size_t)n_pat)) || (rc = dev_alloc(c, &d_pats, pat_bytes)) ||
+        (rc = dev_alloc(c, &d_hits, 1)) || (rc = dev_alloc(c, &ccnt, (size_t)n_chunks)) || (rc = dev_alloc(c, &cbase, (size_t)n_chunks + 1))) {
+        cleanup(); return rc;
+    }
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+    auto destroy_events = [&]() { for (auto &x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(map, 0, sizeof(uint32_t) * (size_t)n2, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess && !blk_row.empty()) {
+        e = hipMemcpyAsync(d_brow, blk_row.data(), sizeof(int32_t) * blk_row.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_bseg, blk_seg.data(), sizeof(int32_t) * blk_seg.size(), hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rp, read_primer, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "mp_offtarget_resident: %s", hipGetErrorString(e)); }
+    FillSeg seg{row_min, sizeof(int32_t) * (size_t)n_rows, 0x7fffffffu};
+    if ((rc = fill_segments(c, &seg, 1))) { destroy_events(); cleanup(); return rc; }
+    OtSites sink{map, c->sq_roff, n_bases, row_min, d_hits};
+    for (auto &T : tables) {
+        if (blk_row.empty()) break;
+        e = hipMemcpyAsync(d_pats, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        if (T.two)
+            hipLaunchKernelGGL((kmm_kernel<2, true, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
+                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
+                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats),
+                               T.n, (int)T.budget, sink);
+        else
+            hipLaunchKernelGGL((kmm_kernel<1, true, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
+                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
+                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<1> *>(d_pats),
+                               T.n, (int)T.budget, sink);
+        e = hipGetLastError();
+        // the next table overwrites d_pats: the copy waits for this launch on the stream, the host array stays alive until the end
+        if (e != hipSuccess) break;
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+    // reduce: the map's sites in order
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(map_count_kernel, dim3(grid(n2, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n2, ccnt);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget scan: %s", hipGetErrorString(e)); }
+    if ((rc = scan_i64(c, ccnt, n_chunks, cbase))) { (void)hipStreamSynchronize(c->stream); destroy_events(); cleanup(); return rc; }
+    unsigned long long h_hits = 0;
+    e = hipMemcpyAsync(&n_sites, cbase + n_chunks, sizeof n_sites, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_hits, d_hits, sizeof h_hits, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the pattern tables may go now)
+    if (e != hipSuccess) { destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget reduce: %s", hipGetErrorString(e)); }
+    ns = (size_t)std::max<long long>(n_sites, 1);
+    if ((rc = dev_alloc(c, &skey, ns)) || (rc = dev_alloc(c, &primer, ns))) { destroy_events(); cleanup(); return rc; }
+    hipLaunchKernelGGL(map_write_kernel, dim3(grid(n2, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n2, (const long long *)cbase,
+                       (const int32_t *)d_rp, skey, primer);
+    e = hipGetLastError();
+    dev_free(c, &map, (size_t)n2);                                  // (released blocks are ordered on the stream: pool_give records an event)
+    if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget reduce: %s", hipGetErrorString(e)); }
+    rc = join_device(c, skey, primer, n_sites, c->sq_roff, n_rows, n_bases, row_min, size_lo, size_hi);
+    if (rc == MP_OK) {
+        e = hipEventRecord(ev[3], c->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
+        float ms = 0;
+        for (int i = 0; i < 3 && e == hipSuccess; i++) { e = hipEventElapsedTime(&ms, ev[i], ev[i + 1]); c->ot_ms[i] = ms; }
+        if (e != hipSuccess) rc = fail(c, MP_ERR_DEVICE, "offtarget timing: %s", hipGetErrorString(e));
+    }
+    destroy_events();
+    cleanup();
+    if (rc != MP_OK) return rc;
+    c->ot_counts[0] = (int64_t)h_hits;
+    c->ot_key = std::move(key);
+    rc = copy_out(c, cap, out, n_out);
+    c->ot_ms[3] = ms_since(t0);
+    return rc;
+}
+
+int mp_amplicon_join(mp_ctx *c, int64_t n_sites, const int32_t *sites, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {
+    if (!c) return MP_ERR_ARG;
+    if (n_sites < 0 || !n_out || cap < 0 || (cap && !out) || (n_sites && !sites)) return fail(c, MP_ERR_ARG, "mp_amplicon_join: bad arguments");
+    HIPCK(c, hipSetDevice(c->dev));
+    const auto t0 = std::chrono::steady_clock::now();
+    *n_out = 0;
+    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+    // explicit sites replace whatever the resident screen kept
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
+    c->ot_n = 0;
+    c->ot_key.clear();
+    if (n_sites == 0) return MP_OK;
+    int32_t max_row = 0;
+    for (int64_t i = 0; i < n_sites; i++) {
+        const int32_t *s = sites + 4 * i;
+        if ((s[0] != 0 && s[0] != 1) || s[1] < 0 || s[2] < 0) return fail(c, MP_ERR_ARG, "mp_amplicon_join: site %lld is not {0|1, row >= 0, pos >= 0, id}", (long long)i);
+        if (s[1] >= (1 << 29)) return fail(c, MP_ERR_ARG, "mp_amplicon_join: row %d of site %lld: at most 2^29 rows", s[1], (long long)i);
+        if (i) {
+            const int32_t *p = s - 4;
+            if (std::make_tuple(p[0], p[1], p[2]) >= std::make_tuple(s[0], s[1], s[2]))
+                return fail(c, MP_ERR_ARG, "mp_amplicon_join: sites must ascend strictly in (strand, row, position) (site %lld)", (long long)i);
+        }
+        max_row = std::max(max_row, s[1]);
+    }
+    const int n_rows = max_row + 1;
+    const long long n_bases = (long long)n_rows << 32;
+    std::vector<long long> key((size_t)n_sites);
+    std::vector<int32_t> primer((size_t)n_sites), row_key((size_t)n_rows);
+    std::vector<int64_t> roff((size_t)n_rows + 1);
+    for (int64_t i = 0; i < n_sites; i++) {
+        const int32_t *s = sites + 4 * i;
+        key[(size_t)i] = (s[0] ? n_bases : 0) + ((long long)s[1] << 32) + s[2];
+        primer[(size_t)i] = s[3];
+    }
+    for (int r = 0; r <= n_rows; r++) roff[(size_t)r] = (int64_t)r << 32;
+    for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;
+    long long *d_key = nullptr;
+    int32_t *d_primer = nullptr, *d_rkey = nullptr;
+    int64_t *d_roff = nullptr;
+    const size_t ns = (size_t)n_sites, nr = (size_t)n_rows;
+    auto cleanup = [&]() { dev_free(c, &d_key, ns); dev_free(c, &d_primer, ns); dev_free(c, &d_rkey, nr); dev_free(c, &d_roff, nr + 1); };
+    int rc;
+    if ((rc = dev_alloc(c, &d_key, ns)) || (rc = dev_alloc(c, &d_primer, ns)) || (rc = dev_alloc(c, &d_rkey, nr)) || (rc = dev_alloc(c, &d_roff, nr + 1))) {
+        cleanup(); return rc;
+    }
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_key, key.data(), sizeof(long long) * ns, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_primer, primer.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rkey, row_key.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    rc = e == hipSuccess ? join_device(c, d_key, d_primer, n_sites, d_roff, n_rows, n_bases, d_rkey, size_lo, size_hi)
+                         : fail(c, MP_ERR_DEVICE, "mp_amplicon_join: %s", hipGetErrorString(e));
+    if (rc == MP_OK) {
+        e = hipEventRecord(ev[1], c->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        c->ot_ms[2] = ms;
+        if (e != hipSuccess) rc = fail(c, MP_ERR_DEVICE, "mp_amplicon_join: %s", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);               // (the host arrays above leave scope)
+    for (auto &x : ev) if (x) (void)hipEventDestroy(x);
+    cleanup();
+    if (rc == MP_OK) rc = copy_out(c, cap, out, n_out);
+    // what the join made stays only for this call's copy: it belongs to no store
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
+    c->ot_n = 0;
+    c->ot_ms[3] = ms_since(t0);
+    return rc;
+}
+
+int mp_offtarget_stats(mp_ctx *c, double *ms, int64_t *counts) {
+    if (!c) return MP_ERR_ARG;
+    for (int i = 0; i < 4; i++) if (ms) ms[i] = c->ot_ms[i];
+    for (int i = 0; i < kOtCounts; i++) if (counts) counts[i] = c->ot_counts[i];
+    return MP_OK;
+}
+
+}  // extern "C"

@@ -88,3 +88,44 @@ def to_fasta(rows: np.ndarray, row0: int = 0) -> bytes:
         parts.append(rows[i].tobytes())
         parts.append(b"\n")
     return b"".join(parts)
+
+
+_COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def offtarget_case(directory, n_rows: int, row_len: int, n_primers: int, seed: int, n_degenerate: int = 2, plant_len: int = 9):
+    """An off-target screen's input (scripts/primer_specificity.py): `n_rows` uniform-random sequences of `row_len` bases as
+    <directory>/background.fa and `n_primers` 20-base primers as <directory>/primers.fa, each with `n_degenerate` N and one R
+    inside its last 9 bases (2 * 4^n expansions of a 9-base term).  Sequence 0 carries planted sites of the first two primers'
+    `plant_len`-base terms (the first expansion: R -> A, N -> C): forward exact at 100, forward with one mismatch at its second base at
+    600, forward with a mismatch at its second-last base (inside a 3' term of 2 or more) at 1100, and the reverse complement of the
+    second primer's term 200, 201 and 202 bases behind them.  Returns (primers path, background path)."""
+    import os
+    rng = np.random.default_rng([seed, 0x5EC])
+    primers = []
+    for _ in range(n_primers):
+        p = bytearray(_ACGT[rng.integers(0, 4, size=20)].tobytes())
+        for j, pos in enumerate(rng.choice(np.arange(11, 16), size=n_degenerate + 1, replace=False)):
+            p[pos] = ord("R") if j == 0 else ord("N")
+        primers.append(p.decode())
+    rows = _ACGT[rng.integers(0, 4, size=(n_rows, row_len), dtype=np.uint8)]
+    if row_len >= 2000 and n_primers >= 2:
+        conc = [p[-plant_len:].replace("R", "A").replace("N", "C") for p in primers[:2]]
+        fwd, rev_rc = conc[0].encode(), conc[1].encode().translate(_COMP)[::-1]
+        one = bytearray(fwd)
+        one[1] = ord("A") if one[1] != ord("A") else ord("C")          # one mismatch away from the 3' end
+        bad = bytearray(fwd)
+        bad[-2] = ord("A") if bad[-2] != ord("A") else ord("C")        # mismatch inside the 3' term
+        for k, (site, at) in enumerate(((fwd, 100), (bytes(one), 600), (bytes(bad), 1100))):
+            rows[0, at:at + plant_len] = np.frombuffer(site, np.uint8)
+            rows[0, at + 200 + k:at + 200 + k + plant_len] = np.frombuffer(rev_rc, np.uint8)
+    os.makedirs(directory, exist_ok=True)
+    pf, bf = os.path.join(directory, "primers.fa"), os.path.join(directory, "background.fa")
+    with open(pf, "w") as f:
+        f.writelines(f">P{i}\n{p}\n" for i, p in enumerate(primers))
+    with open(bf, "wb") as f:
+        for i in range(n_rows):
+            f.write(b">bg%06d synthetic\n" % i)
+            f.write(rows[i].tobytes())
+            f.write(b"\n")
+    return pf, bf

@@ -102,6 +102,30 @@ def sites_of_sam(path, threshold):
     return sites
 
 
+def usable_reads(seqs, names):
+    """Indices of the reads the scan takes (warning about the others on stderr; a read too long for the scan is an error)."""
+    # The reference hands every read to bowtie2, which ignores what it cannot align (an empty read from a blank line of the
+    # primer file — V9 get_term keeps it as key "" —, a read with U / I / N left after expansion, a read shorter than a seed).
+    # This build does the same: such reads find nothing, with a warning naming them; only when NO read is usable is that an
+    # error.  A read BEYOND the packed pattern width is different: bowtie2 would map it, the scan cannot — reporting "no
+    # off-target" for a read that was never looked for would be wrong, so that is a hard error naming the read
+    # (INTEGRATION.md, "Limits": use -l to map the 3' term of longer primers).
+    too_long = [names[i] for i, seq in enumerate(seqs) if len(seq) > PATTERN_MAX_LEN]
+    if too_long:
+        raise ValueError("read(s) longer than the scan's {} bases: {} — map the 3' term instead (-l)".format(
+            PATTERN_MAX_LEN, ", ".join(repr(n) for n in too_long[:20]) + (" ..." if len(too_long) > 20 else "")))
+    usable = [i for i, seq in enumerate(seqs) if len(seq) >= 4 and not (set(seq.upper()) - set("ACGT"))]
+    usable_set = set(usable)
+    skipped = [names[i] for i in range(len(seqs)) if i not in usable_set]
+    if skipped:
+        print("Warning: {} read(s) not scanned (empty, shorter than 4 bases, or not ACGT after expansion), as bowtie2 ignores them: {}".format(
+            len(skipped), ", ".join(repr(n) for n in skipped[:20]) + (" ..." if len(skipped) > 20 else "")),
+            file=sys.stderr)
+    if not usable:
+        raise ValueError(f"no usable read: the scan takes 4..{PATTERN_MAX_LEN} bases of ACGT after expansion")
+    return usable
+
+
 def amplicons(forward, reverse, size_lo, size_hi):
     """(start, stop, forward primer, reverse primer, length) of one sequence, in the reference's order (V9:318-345): starts
     ascending, stops ascending, length = stop - start + 1 strictly inside (size_lo, size_hi).  Two quirks are kept: no product
@@ -158,25 +182,7 @@ class off_targets(object):
         data, row_off = fa.rows()
         genes = [s[1:] if s.startswith(">") else s for s in fa.ids]          # a mapper names a sequence by its first token
         seqs, names = list(table.reads), table.names()
-        # The reference hands every read to bowtie2, which ignores what it cannot align (an empty read from a blank line of the
-        # primer file — V9 get_term keeps it as key "" —, a read with U / I / N left after expansion, a read shorter than a seed).
-        # This build does the same: such reads find nothing, with a warning naming them; only when NO read is usable is that an
-        # error.  A read BEYOND the packed pattern width is different: bowtie2 would map it, the scan cannot — reporting "no
-        # off-target" for a read that was never looked for would be wrong, so that is a hard error naming the read
-        # ("Limits": use -l to map the 3' term of longer primers).
-        too_long = [names[i] for i, seq in enumerate(seqs) if len(seq) > PATTERN_MAX_LEN]
-        if too_long:
-            raise ValueError("read(s) longer than the scan's {} bases: {} — map the 3' term instead (-l)".format(
-                PATTERN_MAX_LEN, ", ".join(repr(n) for n in too_long[:20]) + (" ..." if len(too_long) > 20 else "")))
-        usable = [i for i, seq in enumerate(seqs) if len(seq) >= 4 and not (set(seq.upper()) - set("ACGT"))]
-        usable_set = set(usable)
-        skipped = [names[i] for i in range(len(seqs)) if i not in usable_set]
-        if skipped:
-            print("Warning: {} read(s) not scanned (empty, shorter than 4 bases, or not ACGT after expansion), as bowtie2 ignores them: {}".format(
-                len(skipped), ", ".join(repr(n) for n in skipped[:20]) + (" ..." if len(skipped) > 20 else "")),
-                file=sys.stderr)
-        if not usable:
-            raise ValueError(f"no usable read: the scan takes 4..{PATTERN_MAX_LEN} bases of ACGT after expansion")
+        usable = usable_reads(seqs, names)
         lib = self._library if self._library is not None else Library()
         ctx = lib.context(self._device)
         found = []

@@ -174,5 +174,10 @@ soak)            # profiles/r06_soak.txt: randomised HIP-vs-oracle soaks through
   (timeout 500 python tools/soak_parity.py --seconds ${1:-240} --seed 61; timeout 200 python tools/soak_parity.py --seconds 60 --seed 62; timeout 200 python tools/soak_primers.py --seconds 45) 2>&1 | tee $O/soak.txt ;;
 side_counters)   # profiles/r06_side_kernels.json (+ .txt): kernel trace and FETCH_SIZE / WRITE_SIZE passes of tools/side_bench.py, per kernel
   python tools/side_counters.py --out $O 2>&1 | tee $O/side_kernels_counters.txt ;;
+offtarget)       # profiles/offtarget_scale.txt: the off-target screen, device path against host path, 10^8 / 10^9 bases, 3' terms of 9 / 18 bases
+  # (pipefail: a failed, faulted or timed-out test run ends the target before the bench starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_offtarget_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 1500 python tools/offtarget_bench.py --bases 1e8 1e9 --terms 9 18 2>&1 | tee $O/offtarget_scale.txt ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
