@@ -8,6 +8,12 @@ per-candidate coverage counters.  Inputs are resident in HBM (planes built once,
   python bench.py --gpus 1 --steps 20 --warmup 3
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
+A plain run does only what the headline needs: it sets up the workload, warms up, times the steps, writes --dump-outputs if asked and
+prints ONE line (metric, value, unit, ms_per_step, steps_in_flight, config, ...).  Everything below that takes a measurement or a check
+of its own runs only with `--full`: the one-stream pass and the roofline, the CPU oracle and its parity check, the side blocks, the
+copy bandwidth, the counter checksum, the bucketed collective and the library communicator (N > 1).  A `--full` run at N = 1 measures
+in a child process (supervise()), writes every block to bench_detail.json and prints the headline with `roofline` and `cpu_baseline`.
+
 The workload is config 4 at every N: 1 048 576 x 1000 rows in all, 1 048 576 / N per GPU (`scaling: "strong"`).  At N = 1 the
 headline (`value`, `ms_per_step`, `config.workload`, `roofline`, `cpu_baseline`) is config 4 itself on one GPU — the one size
 where HBM can bind (planes 0.5 GB > Infinity Cache).  `--rows R` fixes the rows per GPU instead (weak scaling, `scaling: "weak"`).
@@ -69,7 +75,7 @@ from bench_blocks import (OracleBlocks, cpu_baseline, k_sweep, pipeline_block, p
                           weak_shard)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
@@ -82,23 +88,29 @@ def main():
     ap.add_argument("--seed", type=int, default=20250303)
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the workload the CPU oracle evaluates (0 = all of them)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host threads of the all-core CPU leg (0 = every core)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-pipeline", action="store_true", help="N = 1: skip the `pipeline` block (NN_degenerate.run() on the same rows)")
-    ap.add_argument("--no-shapes", action="store_true", help="N = 1: skip the `shard_shapes` block (one rank's share of the 2-D shards 4x2, 2x4, 1x8)")
-    ap.add_argument("--no-ksweep", action="store_true", help="N = 1: skip the `k_sweep` block (the headline workload at k = 20, 22, 36)")
-    ap.add_argument("--no-side", action="store_true", help="N = 1: skip the `side_steps` block (dimer scan, in-silico PCR, k-mismatch scan: tools/side_bench.py)")
-    ap.add_argument("--no-shard", "--no-full", dest="no_shard", action="store_true",
-                    help="N = 1: skip the weak_shard block (the 131072-row shard of the 8-GPU job)")
+    ap.add_argument("--full", action="store_true", help="also every side measurement and check: roofline, CPU oracle and parity, variants, pipeline, shard, "
+                    "shapes, k sweep, side steps (N = 1); checksum parity, bucketed collective, library communicator (N > 1); bench_detail.json")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU oracle legs (and their parity checks)")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the `variants` blocks")
+    ap.add_argument("--no-pipeline", action="store_true", help="--full, N = 1: skip the `pipeline` block (NN_degenerate.run() on the same rows)")
+    ap.add_argument("--no-shapes", action="store_true", help="--full, N = 1: skip the `shard_shapes` block (one rank's share of the 2-D shards 4x2, 2x4, 1x8)")
+    ap.add_argument("--no-ksweep", action="store_true", help="--full, N = 1: skip the `k_sweep` block (the headline workload at k = 20, 22, 36)")
+    ap.add_argument("--no-side", action="store_true", help="--full, N = 1: skip the `side_steps` block (dimer scan, in-silico PCR, k-mismatch scan: tools/side_bench.py)")
+    ap.add_argument("--no-shard", action="store_true", help="--full, N = 1: skip the weak_shard block (the 131072-row shard of the 8-GPU job)")
     ap.add_argument("--shape", default=None, metavar="RxG|auto", help="N > 1: R row shards x G window groups (R x G = N); default auto = as many window "
                     "groups as the device memory allows (dist.ShardGrid.best_shape); Nx1 = row shards only")
     ap.add_argument("--share", default=None, metavar="RxG", help="N = 1 experiment: time one rank's share of an R x G job instead of the whole workload")
-    ap.add_argument("--bucket", type=int, default=4, help="steps per collective of the bucketed side measurement (N > 1)")
+    ap.add_argument("--bucket", type=int, default=4, help="--full, N > 1: steps per collective of the bucketed side measurement")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the counters of the headline's last timed step to DIR/*.npy "
                     "(float64), to compare two builds output for output on the same seeded inputs")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def main(a=None):
+    a = a or parse_args()
     import faulthandler
     faulthandler.enable()           # a fatal signal leaves every thread's Python stack on stderr (the driver keeps stderr)
     t_main = time.time()
@@ -232,9 +244,9 @@ def main():
         return float(tt[0].item()), kern_ms, kern_n, samples, sb, (-float(tt[1].item()), float(tt[0].item())), 2 if use2 else 1
 
     def timed_pair(wl, n_world, n_reduce=None, group=None):
-        """The headline's timed region and, when that overlapped its steps on two streams, a second one on ONE stream for the kernel's own
-        duration (HIP events around single launches: the roofline's kernel time) — (elapsed, kernel ms, launches timed, samples, buckets,
-        spread, streams of the first region, ms per step on one stream)."""
+        """The headline's timed region and, with --full, when that overlapped its steps on two streams, a second one on ONE stream for the
+        kernel's own duration (HIP events around single launches: the roofline's kernel time) — (elapsed, kernel ms, launches timed, samples,
+        buckets, spread, streams of the first region, ms per step on one stream or None when not measured)."""
         pick = None
         if n_world == 1 and two_streams and "MP_BENCH_STREAMS" not in os.environ:
             # one GPU: the launch strategy is chosen by a short trial of both (a kernel that fills the chip for 140 us gains nothing from a
@@ -242,8 +254,8 @@ def main():
             trial = {st: min(timed_region(wl, 1, 1, streams=st, steps=12)[0] for _ in range(2)) for st in (1, 2)}
             pick = min(trial, key=trial.get)
         elapsed, kern_ms, kern_n, samples, sb, spread, used = timed_region(wl, 1, n_world, n_reduce, group, streams=pick)
-        one_ms = elapsed / a.steps * 1e3
-        if used == 2:
+        one_ms = elapsed / a.steps * 1e3 if used == 1 else None
+        if used == 2 and a.full:
             e1, kern_ms, kern_n, samples, _, _, _ = timed_region(wl, 1, 1, streams=1)
             one_ms = e1 / a.steps * 1e3
         return elapsed, kern_ms, kern_n, samples, sb, spread, used, one_ms
@@ -251,7 +263,7 @@ def main():
     elapsed, kern_ms, kern_n, samples, sb, spread, streams_used, one_stream_ms = timed_pair(w, world, R, row_group)
     gpu_counters = sb.block_of(a.steps - 1).cpu().numpy().copy()       # [n_cand][3], summed over ranks when N > 1
     bucketed = None
-    if world > 1 and a.bucket > 1:
+    if a.full and world > 1 and a.bucket > 1:
         e1, *_ = timed_region(w, a.bucket, world, R, row_group, streams=1)
         bucketed = e1
 
@@ -262,10 +274,12 @@ def main():
     # the counters of every candidate summed: over the window groups (their leaders, row shard 0, hold a group's reduced counters) this is the
     # checksum of the whole workload — at N = 1 it comes out of the run whose counters are compared with the oracle's one by one, so a
     # committed value lets an N > 1 run (no oracle leg there) say whether ITS counters are the same
-    cs = torch.tensor(gpu_counters.sum(axis=0) if ri == 0 else np.zeros(3, np.int64), dtype=torch.int64, device=dev)
-    if world > 1:
-        dist.all_reduce(cs, op=dist.ReduceOp.SUM)
-    checksum = [int(x) for x in cs.tolist()]
+    checksum = None
+    if a.full:
+        cs = torch.tensor(gpu_counters.sum(axis=0) if ri == 0 else np.zeros(3, np.int64), dtype=torch.int64, device=dev)
+        if world > 1:
+            dist.all_reduce(cs, op=dist.ReduceOp.SUM)
+        checksum = [int(x) for x in cs.tolist()]
     if a.dump_outputs:
         # the whole [n_cand][3] result of the last timed step: every window group's slice (reduced over its row group), in window order
         parts = [(gi, gpu_counters)] if ri == 0 else []
@@ -278,11 +292,11 @@ def main():
 
     # what the communicator itself says (N > 1): the ranks RCCL saw, through a communicator of the library's own
     comm_info = None
-    if world > 1:
+    if a.full and world > 1:
         comm_info = {"backend": backend, "torch_world": dist.get_world_size()}
     # measured device-copy bandwidth (SURVEY §8d asks for it next to the spec peak): 1 GiB d2d, read + write
     copy_gbs = None
-    if rank == 0:
+    if a.full and rank == 0:
         src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -297,8 +311,6 @@ def main():
 
     res = None
     if rank == 0:
-        mode = eval_mode(w.n_rows, ctx)
-        per_launch_ms = kern_ms / max(kern_n, 1)
         whole = "BASELINE configs[3] itself" if strong else f"{world * rows_per_gpu} rows in all"
         res = {
             "metric": "candidate x sequence coverage evals/s",
@@ -306,7 +318,7 @@ def main():
             "unit": "evals/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": elapsed / a.steps * 1e3,
-            "steps_in_flight": streams_used, "ms_per_step_one_stream": one_stream_ms,
+            "steps_in_flight": streams_used,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": "u32", "data": "synthetic",
             "config": {"workload": f"{w.describe()} per GPU x {world} GPU(s) = {whole} (SURVEY 8d input 4; synthetic 1M x 1 kb; shape {R}x{G}: row shards x window groups)",
@@ -316,20 +328,23 @@ def main():
                        "parallelism": ("one GPU holds every row" if world == 1 else
                                        f"{G} window groups x 1 row shard: every GPU holds every row and evaluates 1/{G} of the windows, no collective" if R == 1 else
                                        f"{R} row shards x {G} window group(s): one RCCL all-reduce of the [{n_cand}x3] int64 counters per step inside a row group of {R} ranks")},
-            "roofline": roofline_block(w, per_launch_ms, samples, kern_n, every, mode),
-            "measured_copy_GBs": copy_gbs, "setup_s": w.setup_s, "device_bytes": ctx.device_bytes(), "counter_checksum": checksum,
         }
+        if a.full:
+            res.update({"ms_per_step_one_stream": one_stream_ms,
+                        "roofline": roofline_block(w, kern_ms / max(kern_n, 1), samples, kern_n, every, eval_mode(w.n_rows, ctx)),
+                        "measured_copy_GBs": copy_gbs, "setup_s": w.setup_s, "device_bytes": ctx.device_bytes(), "counter_checksum": checksum})
         default_workload = strong and (a.k, a.v, a.cands, a.cols, a.seed) == (18, 1, 8, 1000, 20250303)
-        if world > 1 and default_workload:
+        if a.full and world > 1 and default_workload:
             res["parity_checked"] = checksum == CONFIG4_CHECKSUM
             res["parity_note"] = "the sum of all candidates' counters equals the N = 1 run's, whose counters were compared with the oracle's one by one"
         if world > 1:
             res["step_time_ranks_ms"] = {"min": spread[0] / a.steps * 1e3, "max": spread[1] / a.steps * 1e3}
+        if comm_info is not None:
             res["comm"] = comm_info
         if bucketed is not None:
             res["ms_per_step_bucketed"] = bucketed / a.steps * 1e3
             res["bucket"] = a.bucket
-        if world == 1:
+        if a.full and world == 1:
             res["step_form"] = ("rotating: the launch that fills a step's counter block clears the next step's inside its own grid (mp_eval_launch_rotating)"
                                 if rotate else "a fill dispatch in front of every evaluation (mp_eval_launch; MP_BENCH_ROTATE=0)")
             progress("cpu_baseline")
@@ -371,7 +386,7 @@ def main():
                                    f"rows_{rows_per_gpu}": pipeline_block(lib, local, w.rows, a)}
     # N = 1: the shard one GPU holds in the 8-GPU job, timed the same way (with the variant measurements)
     progress("weak_shard")
-    if rank == 0 and world == 1 and not a.no_shard and rows_per_gpu != SHARD_ROWS:
+    if a.full and rank == 0 and world == 1 and not a.no_shard and rows_per_gpu != SHARD_ROWS:
         sb = None
         if w.ctx is not None:
             w.ctx.close()
@@ -426,7 +441,7 @@ def main():
         res["parity_checked"] = False
     # N = 1: the steps either side of the core step, each with its checker leg — detail file only
     progress("side_steps")
-    if rank == 0 and world == 1 and not a.no_side:
+    if a.full and rank == 0 and world == 1 and not a.no_side:
         try:
             sys.path.insert(0, os.path.join(REPO, "tools"))
             import side_bench
@@ -438,7 +453,7 @@ def main():
     # N > 1: what the communicator itself says, through a communicator of the library's own (csrc/comm.hip) — AFTER everything the headline needs
     # exists, and under a watchdog: this path has only ever run on stand-ins (gloo ranks, the shared-memory stub of librccl), a communicator
     # that never answers must not take the measured line with it.  After 120 s rank 0 prints the line without it and every rank leaves.
-    if world > 1 and backend == "nccl" and os.environ.get("MP_BENCH_LIBCOMM", "1") != "0":
+    if a.full and world > 1 and backend == "nccl" and os.environ.get("MP_BENCH_LIBCOMM", "1") != "0":
         def give_up():
             if rank == 0:
                 comm_info["library_communicator_error"] = "no answer within 120 s"
@@ -461,7 +476,10 @@ def main():
         dog.cancel()
     progress("emit")
     if rank == 0:
-        emit(res)
+        if a.full:
+            emit(res)
+        else:
+            print(headline(res, detail=False), flush=True)          # a plain run: the headline alone, no detail file
     if world > 1:
         # the line is out: a rank that left through the watchdog above must not keep the others in this barrier for the collective's own timeout
         bad = bool(res.get("parity_checked") is False) if rank == 0 else False
@@ -489,10 +507,11 @@ def _sig(x, digits=6):
     return x
 
 
-def headline(res):
+def headline(res, detail=True):
     """The ONE line the driver parses: the contract's keys, `roofline` and `cpu_baseline` of the headline kernel, the parity verdict and
     the projected scaling ceiling — no notes, no tables, no nested side measurements (those go to bench_detail.json and to an
-    earlier, prefixed stdout line).  Always shorter than HEADLINE_LIMIT (tests/test_bench_line.py)."""
+    earlier, prefixed stdout line).  A plain run (no --full) has no roofline, CPU leg or detail file, and its line names none of them.
+    Always shorter than HEADLINE_LIMIT (tests/test_bench_line.py)."""
     top = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
            "parity_checked", "ms_per_step_bucketed", "bucket", "steps_in_flight", "ms_per_step_one_stream", "provisional")
     out = {key: res[key] for key in top if key in res}
@@ -500,15 +519,16 @@ def headline(res):
     out["config"] = {key: cfg[key] for key in ("workload", "rows_per_gpu", "rows_total", "cols", "k", "variation", "candidates_per_window", "windows",
                                                "evals_per_step_per_gpu", "shape", "parallelism") if key in cfg}
     out["config"]["workload"] = str(out["config"].get("workload", ""))[:240]
-    rf = res.get("roofline") or {}
+    rf = res.get("roofline")
     # `bound` of the contract is the roofline `peak` belongs to (HBM; integer bit-mask work has no MFMA roofline); `limiter` is the
     # largest of the measured fractions (valu / l2 / hbm), i.e. what actually binds the kernel
-    out["roofline"] = {"bound": "hbm", "achieved": rf.get("achieved"), "peak": rf.get("peak"), "unit": rf.get("unit"), "frac": rf.get("frac"),
-                       "traffic": rf.get("traffic"), "hbm_frac": rf.get("hbm_frac"), "over_fetch": rf.get("over_fetch"),
-                       "valu_frac": rf.get("valu_frac"), "l2_frac": rf.get("l2_frac"), "limiter": rf.get("bound"),
-                       "algorithmic_frac": rf.get("algorithmic_frac"), "compulsory_bytes": rf.get("compulsory_bytes"),
-                       "kernel": str(rf.get("kernel", "")).split(" (")[0], "eval_mode": rf.get("eval_mode"), "kernel_ms": rf.get("kernel_ms"),
-                       "counters_stale": rf.get("counters_stale")}
+    if rf is not None:
+        out["roofline"] = {"bound": "hbm", "achieved": rf.get("achieved"), "peak": rf.get("peak"), "unit": rf.get("unit"), "frac": rf.get("frac"),
+                           "traffic": rf.get("traffic"), "hbm_frac": rf.get("hbm_frac"), "over_fetch": rf.get("over_fetch"),
+                           "valu_frac": rf.get("valu_frac"), "l2_frac": rf.get("l2_frac"), "limiter": rf.get("bound"),
+                           "algorithmic_frac": rf.get("algorithmic_frac"), "compulsory_bytes": rf.get("compulsory_bytes"),
+                           "kernel": str(rf.get("kernel", "")).split(" (")[0], "eval_mode": rf.get("eval_mode"), "kernel_ms": rf.get("kernel_ms"),
+                           "counters_stale": rf.get("counters_stale")}
     cb = res.get("cpu_baseline")
     if cb:
         out["cpu_baseline"] = {"value": cb.get("value"), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),
@@ -528,7 +548,8 @@ def headline(res):
         out["comm"] = {key: res["comm"][key] for key in ("backend", "rccl_ranks_seen", "sum_of_ones") if key in res["comm"]}
     if "step_time_ranks_ms" in res:
         out["step_time_ranks_ms"] = res["step_time_ranks_ms"]
-    out["detail"] = "bench_detail.json"
+    if detail:
+        out["detail"] = "bench_detail.json"
     out = _sig(out)
     line = json.dumps(out, separators=(",", ":"))
     for drop in ("pipeline", "comm", "step_time_ranks_ms", "projected_strong_scaling"):       # never reached with the fields above; the limit holds regardless
@@ -574,7 +595,7 @@ def dump_outputs(d, counters):
 
 
 def supervise(cmd, env=None, out=None, attempts=2):
-    """N = 1: the measuring runs in a CHILD process and this one only relays its stdout.  A fatal signal inside the runtime cannot be caught
+    """--full at N = 1: the measuring runs in a CHILD process and this one only relays its stdout.  A fatal signal inside the runtime cannot be caught
     in the process it hits (round 6: two of 57 runs died in a side measurement, never reproduced in isolation — DESIGN 9.-2); from here it can:
       * the child's last line is a final headline           -> nothing to add, its exit status is ours (non-zero when parity failed);
       * the child ended after the PROVISIONAL headline      -> that line again as the last line, `side_measurements` saying what happened, exit 0
@@ -619,9 +640,10 @@ def supervise(cmd, env=None, out=None, attempts=2):
 
 
 if __name__ == "__main__":
+    args = parse_args()
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or "ROCP_TOOL_LIBRARIES" in os.environ      # rocprofv3: one process, one trace
-    if "RANK" in os.environ or profiled or os.environ.get("MP_BENCH_CHILD") or os.environ.get("MP_BENCH_NO_SUPERVISOR"):
-        main()                      # a rank of torch.distributed.run, a profiled run, or the child below
+    if not args.full or "RANK" in os.environ or profiled or os.environ.get("MP_BENCH_CHILD") or os.environ.get("MP_BENCH_NO_SUPERVISOR"):
+        main(args)                  # a plain run (no side blocks to survive), a rank of torch.distributed.run, a profiled run, or the child below
     else:
         sys.exit(supervise([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env={**os.environ, "MP_BENCH_CHILD": "1"}))
 

@@ -3,6 +3,8 @@ import importlib.util
 import json
 import os
 
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -62,6 +64,27 @@ def test_provisional_headline_is_a_complete_contract_line():
     assert src.index('"provisional": True') < src.index('progress("variants")') < src.index("emit(res)")
 
 
+def test_headline_of_a_plain_run_names_no_side_measurement():
+    """Without --full bench.py measures the headline alone: its line carries the contract's keys and nothing that a side measurement fills."""
+    bench = _bench()
+    with open(os.path.join(REPO, "profiles", "r05_bench_default_flags.json")) as f:
+        res = json.load(f)
+    contract = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+    plain = {key: res[key] for key in contract + ("n_gpus", "steps", "warmup", "scaling", "vs_baseline", "data", "config")}
+    plain["steps_in_flight"] = 2
+    out = json.loads(bench.headline(plain, detail=False))
+    for key in contract:
+        assert out[key] == (bench._sig(plain[key]) if isinstance(plain[key], float) else plain[key]), key
+    assert not {"roofline", "cpu_baseline", "parity_checked", "projected_strong_scaling", "pipeline", "ms_per_step_one_stream", "detail"} & set(out)
+    assert json.loads(bench.headline(res))["detail"] == "bench_detail.json"
+
+
+def test_side_measurements_wait_for_full():
+    bench = _bench()
+    assert bench.parse_args(["--steps", "3"]).full is False
+    assert bench.parse_args(["--full", "--no-shard"]).full is True
+
+
 def _fake_child(tmp_path, body):
     path = tmp_path / "child.py"
     path.write_text("import json, os, signal, sys\n" + body)
@@ -110,3 +133,25 @@ def test_dump_outputs_writes_float64_counters_within_the_limit(tmp_path, monkeyp
     assert len(idx) == 100 and np.all(np.diff(idx) > 0) and np.array_equal(got.astype(np.int64), counters[idx.astype(np.int64)])
     assert idx.nbytes + got.nbytes <= bench.DUMP_LIMIT
     assert np.array_equal(idx, np.load(tmp_path / "s2" / "coverage_counters_index.npy"))     # the same sample every run
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_one_headline_and_writes_only_the_dump(tmp_path):
+    """A plain run on the GPU: exit 0, one stdout line (the headline, no roofline / oracle leg), the counters under --dump-outputs, no detail file."""
+    import subprocess
+    import sys
+    import numpy as np
+    detail = os.path.join(REPO, "bench_detail.json")
+    before = os.path.getmtime(detail) if os.path.exists(detail) else None
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--rows", "131072",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "candidate x sequence coverage evals/s" and out["unit"] == "evals/s" and out["dtype"] == "u32"
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["steps"] == 4 and out["warmup"] == 1
+    assert not {"roofline", "cpu_baseline", "parity_checked", "detail"} & set(out)
+    got = np.load(tmp_path / "out" / "coverage_counters.npy")
+    assert got.dtype == np.float64 and got.shape == (out["config"]["windows"] * out["config"]["candidates_per_window"], 3)
+    assert (os.path.getmtime(detail) if os.path.exists(detail) else None) == before

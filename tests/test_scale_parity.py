@@ -130,7 +130,7 @@ def test_committed_synthetic_tsv_is_what_the_checker_computes(oracle_lib, tmp_pa
 @pytest.mark.parametrize("rows_n", [16384, 131072, 1048576])
 def test_core_step_on_the_bench_alignment_equals_the_checker(hip_lib, tmp_path, rows_n):
     """The REAL step (NN_degenerate.run(), --no-json) on the bench's own synthetic rows — incl. BASELINE configs[3]'s 1M x 1 kb on
-    one GPU — writes the TSV the checker wrote (bench.py's `pipeline` block makes the same comparison in every run)."""
+    one GPU — writes the TSV the checker wrote (bench.py's `pipeline` block makes the same comparison in every --full run)."""
     from multiprime_amd.core import NN_degenerate
     sha, entry = _synthetic_tsv_sha(hip_lib, rows_n, tmp_path, NN_degenerate)
     assert sha == entry["tsv_sha256"]

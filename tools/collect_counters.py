@@ -55,7 +55,7 @@ def main():
     a = ap.parse_args()
     a.out = os.path.abspath(a.out)                 # rocprofv3 runs from /tmp
     os.makedirs(a.out, exist_ok=True)
-    bench = [sys.executable, os.path.join(REPO, "bench.py"), "--rows", str(a.rows), "--no-cpu", "--no-variants", "--no-full", "--no-pipeline", "--no-side", "--no-shapes", "--no-ksweep"] + a.bench_args.split()
+    bench = [sys.executable, os.path.join(REPO, "bench.py"), "--rows", str(a.rows), "--full", "--no-cpu", "--no-variants", "--no-shard", "--no-pipeline", "--no-side", "--no-shapes", "--no-ksweep"] + a.bench_args.split()
     # kernel trace of the bench command itself
     run(["rocprofv3", "--kernel-trace", "--stats", "-d", os.path.join(a.out, "trace"), "-o", "bench", "--"] + bench + ["--steps", "20", "--warmup", "3"],
         os.path.join(a.out, "trace_bench.json"))
@@ -143,7 +143,7 @@ def main():
         entry["hbm_read_bytes"] = raw["FETCH_SIZE"] * 1024 * 2      # KB; gfx950 tallies 128-B requests at 64 B (MI355X_MICROARCH.md, HBM)
     if "WRITE_SIZE" in raw:
         entry["hbm_write_bytes"] = raw["WRITE_SIZE"] * 1024
-    entry["source"] = "tools/collect_counters.py: separate rocprofv3 --pmc passes of `python bench.py --steps 5 --warmup 1 --no-cpu --no-variants`, per-dispatch average of the timed kernel"
+    entry["source"] = "tools/collect_counters.py: separate rocprofv3 --pmc passes of `python bench.py --full --steps 5 --warmup 1 --no-cpu --no-variants`, per-dispatch average of the timed kernel"
     entries = [entry]
     if a.merge and os.path.exists(a.merge):          # keep the entries of other configurations collected earlier
         old = json.load(open(a.merge)).get("entries", [])

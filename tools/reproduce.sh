@@ -57,7 +57,7 @@ for k, v in d.items():
   rocprofv3 --kernel-trace --stats -d $O/prof/trace -o t -- python tools/side_bench.py > /dev/null 2>&1
   python tools/summarize_profile.py $O/prof 2>/dev/null | head -24 | tee $O/side_kernels.txt ;;
 shapes)          # bench.py's shard_shapes block alone (headline + 8x1 shard + 4x2 / 2x4 / 1x8), no side measurements
-  timeout 1200 python bench.py --steps 40 --warmup 5 --no-variants --no-pipeline --no-side --no-ksweep "$@" > $O/bench.txt 2> $O/bench.err; tail -c 400 $O/bench.err; tail -1 $O/bench.txt
+  timeout 1200 python bench.py --full --steps 40 --warmup 5 --no-variants --no-pipeline --no-side --no-ksweep "$@" > $O/bench.txt 2> $O/bench.err; tail -c 400 $O/bench.err; tail -1 $O/bench.txt
   python -c "
 import json
 d = json.load(open('bench_detail.json'))
@@ -68,7 +68,7 @@ bench_ranks)     # bench.py's N > 1 control flow on the ONE GPU of a test box: r
   for spec in "2 1x2" "2 2x1" "4 2x2" "4 1x4" "4 auto"; do set -- $spec
     echo "# N=$1 --shape $2"
     MP_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 --master-addr 127.0.0.1 --master-port 29533 \
-      bench.py --gpus $1 --steps 10 --warmup 2 --shape $2 2> $O/err_$1_$2.txt | tail -1 | python -c "
+      bench.py --full --gpus $1 --steps 10 --warmup 2 --shape $2 2> $O/err_$1_$2.txt | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print({k: d[k] for k in ('n_gpus', 'ms_per_step', 'value', 'parity_checked')}, d['config']['shape'], d['config']['parallelism'])"
@@ -76,28 +76,28 @@ print({k: d[k] for k in ('n_gpus', 'ms_per_step', 'value', 'parity_checked')}, d
 share_sweep)     # profiles/r06_share_sweep.txt: one rank's share of the 1x8 / 2x4 / 8x1 job under band lengths and row words per lane of the sliding kernel
   for share in 1x8 2x4 8x1; do for gw in 1 2 4; do for band in 0 4 6 8 10 12 15 20 30; do
     if [ $band = 0 ]; then unset MP_SLIDE_BAND; else export MP_SLIDE_BAND=$band; fi
-    MP_EVAL_SLIDE=1 MP_SLIDE_GW=$gw timeout 300 python bench.py --steps 60 --warmup 5 --share $share --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
+    MP_EVAL_SLIDE=1 MP_SLIDE_GW=$gw timeout 300 python bench.py --full --steps 60 --warmup 5 --share $share --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); print('share $share gw $gw band $band ms_per_step %.5f kernel_ms %.5f' % (d['ms_per_step'], d['roofline']['kernel_ms']))"
   done; done; done 2>&1 | tee $O/share_sweep.txt ;;
 streams)         # one stream (rotating launches) against two (mp_eval_launch_alt): the whole workload and one rank's shares
   for share in "" 1x8 2x4 8x1; do for st in 1 2; do for rep in 1 2; do
-    MP_BENCH_STREAMS=$st timeout 300 python bench.py --steps 80 --warmup 6 ${share:+--share $share} --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
+    MP_BENCH_STREAMS=$st timeout 300 python bench.py --full --steps 80 --warmup 6 ${share:+--share $share} --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); print('share ${share:-1x1} streams $st ms_per_step %.5f kernel_ms %.5f' % (d['ms_per_step'], d['roofline']['kernel_ms']))"
   done; done; done 2>&1 | tee $O/streams.txt ;;
 strict_ab)       # profiles/r06_strict_forms.txt: the sliding kernel's strict positions as two-bit counts per side against position by position (MP_SLIDE_STRICT=0)
   timeout 900 python -m pytest tests/test_hip_parity.py -q -m gpu -x -k "strict_position or grouping_paths or kernel_shapes" 2>&1 | tail -4 | tee $O/pytest.txt
   for rep in 1 2 3; do for st in 0 1; do
-    MP_SLIDE_STRICT=$st timeout 300 python bench.py --steps 80 --warmup 6 --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
+    MP_SLIDE_STRICT=$st timeout 300 python bench.py --full --steps 80 --warmup 6 --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); print('MP_SLIDE_STRICT=$st ms_per_step %.5f one_stream %.5f kernel_ms %.5f' % (d['ms_per_step'], d.get('ms_per_step_one_stream', 0), d['roofline']['kernel_ms']))"
   done; done 2>&1 | tee $O/strict_forms.txt
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-variants --no-pipeline --no-side --no-ksweep --no-shapes 2> $O/bench.err | tail -1 | tee $O/bench_parity.json ;;
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-variants --no-pipeline --no-side --no-ksweep --no-shapes 2> $O/bench.err | tail -1 | tee $O/bench_parity.json ;;
 exp_libs)        # A/B of experiment builds: tools/reproduce.sh exp_libs TAG... (tools/_build/libmprime_hip_TAG.so; `product` = the tree's library), 3 interleaved repetitions
   for rep in 1 2 3; do for tag in "$@"; do
     lib=$PWD/tools/_build/libmprime_hip_$tag.so; [ $tag = product ] && lib=$PWD/multiprime_amd/csrc/libmprime_hip.so
-    MPRIME_LIBRARY=$lib MP_HOST_LIB=$lib MP_BENCH_STREAMS=1 timeout 300 python bench.py --steps 80 --warmup 6 --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
+    MPRIME_LIBRARY=$lib MP_HOST_LIB=$lib MP_BENCH_STREAMS=1 timeout 300 python bench.py --full --steps 80 --warmup 6 --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); print('$tag ms_per_step %.5f kernel_ms %.5f' % (d['ms_per_step'], d['roofline']['kernel_ms']))"
   done; done 2>&1 | tee $O/exp_libs.txt
@@ -114,7 +114,7 @@ compact_ab)      # compact_kernel per piece of a window's table: the suites that
   for rows in 131072 1048576; do python tools/profile_pipeline.py --rows $rows --out $O/prof_$rows 2>&1 | grep "compact\|table_sums\|hist2\|^kernel"; done 2>&1 | tee $O/compact.txt
   MP_TRACE=1 python tools/profile_run.py 1048576 18 2>&1 | grep "unique:\|^{" | tail -8 | cut -c1-400 | tee -a $O/compact.txt; rm -rf $O/prof_* ;;
 k_sweep)         # bench.py's k_sweep block alone (the headline workload at k = 20, 22, 36), after the headline
-  timeout 900 python bench.py --steps 20 --warmup 5 --no-variants --no-pipeline --no-side --no-shapes 2> $O/bench.err | tail -1 > $O/bench.json; python -c "
+  timeout 900 python bench.py --full --steps 20 --warmup 5 --no-variants --no-pipeline --no-side --no-shapes 2> $O/bench.err | tail -1 > $O/bench.json; python -c "
 import json
 d = json.load(open('bench_detail.json'))
 print('k_18', d['ms_per_step'], d['roofline']['kernel_ms'], d['parity_checked'])
@@ -123,7 +123,7 @@ for k, v in d.get('k_sweep', {}).items(): print(k, v if not isinstance(v, dict) 
 exp_rows)        # profiles/r06_exp_one_row.txt: experiment builds of the sliding kernel (tools/build_variant.sh rowN evalslide.hip -DSLIDE_EXP_ONE_ROW=N; wrong results, timing only)
   for rep in 1 2; do for tag in product row1 row2 row3; do
     lib=$PWD/tools/_build/libmprime_hip_$tag.so; [ $tag = product ] && lib=$PWD/multiprime_amd/csrc/libmprime_hip.so
-    MPRIME_LIBRARY=$lib MP_HOST_LIB=$lib MP_BENCH_STREAMS=1 timeout 300 python bench.py --steps 80 --warmup 6 --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
+    MPRIME_LIBRARY=$lib MP_HOST_LIB=$lib MP_BENCH_STREAMS=1 timeout 300 python bench.py --full --steps 80 --warmup 6 --no-variants --no-pipeline --no-side --no-ksweep --no-shard --no-cpu 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); print('$tag ms_per_step %.5f kernel_ms %.5f' % (d['ms_per_step'], d['roofline']['kernel_ms']))"
   done; done 2>&1 | tee $O/exp_one_row.txt
@@ -138,7 +138,7 @@ for e in d['entries']:
     rm -rf $O/prof_strict$st/pmc_* $O/prof_strict$st/cal_* $O/prof_strict$st/trace
   done ;;
 bench_default)   # profiles/r06_bench.json + r06_bench_detail.json: `python bench.py` with the driver's flags, wall time, the blocks of the detail file in short
-  SECONDS=0; python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.txt 2> $O/bench.err; echo "rc=$? wall=${SECONDS}s"; tail -c 300 $O/bench.err
+  SECONDS=0; python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.txt 2> $O/bench.err; echo "rc=$? wall=${SECONDS}s"; tail -c 300 $O/bench.err
   tail -1 $O/bench.txt > $O/bench.json; cp bench_detail.json $O/bench_detail.json; wc -c $O/bench.json; cat $O/bench.json
   python -c "
 import json
@@ -166,7 +166,7 @@ final)           # everything the round's profiles/ files come from, in the orde
   cp $O/prof_1m/summary.txt $O/bench_eval_1m.txt 2>/dev/null; cp $O/prof_131k/summary.txt $O/bench_eval.txt 2>/dev/null
   rocprofv3 --kernel-trace --stats -d $O/prof_side/trace -o t -- python tools/side_bench.py > /dev/null 2>&1
   python tools/summarize_profile.py $O/prof_side 2>/dev/null | head -24 > $O/side_kernels.txt
-  SECONDS=0; python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.txt 2> $O/bench.err; echo "bench rc=$? wall=${SECONDS}s"
+  SECONDS=0; python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.txt 2> $O/bench.err; echo "bench rc=$? wall=${SECONDS}s"
   tail -1 $O/bench.txt > $O/bench.json; cp bench_detail.json $O/bench_detail.json; wc -c $O/bench.json; cat $O/bench.json
   (for rows in 131072 1048576; do for k in 18 22; do echo "# rows $rows k $k"; laps $rows $k; done; done) > $O/run_laps.txt 2>&1
   du -sh $O; rm -rf $O/prof_pipe_* $O/prof_1m/pmc_* $O/prof_131k/pmc_* $O/prof_1m/cal_* $O/prof_131k/cal_* $O/prof_side ;;

@@ -14,10 +14,10 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 PORT=29510
 for N in 1 2 4 8; do
   if [ "$N" = 1 ]; then
-    python bench.py --gpus 1 --steps 20 --warmup 3 > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+    python bench.py --full --gpus 1 --steps 20 --warmup 3 > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((PORT + N)) \
-      bench.py --gpus $N --steps 20 --warmup 3 > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
+      bench.py --full --gpus $N --steps 20 --warmup 3 > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
   fi
   echo "bench N=$N exit $?"
 done
