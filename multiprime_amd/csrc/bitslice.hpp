@@ -194,4 +194,12 @@ __device__ __forceinline__ bool map_block(const BlockMap &M, unsigned b, int &sl
     return slice < M.ny && idx < M.n_items;
 }
 
+// host side (eval.hip), shared with stats.hip:
+// workgroups of a bit-sliced launch: n_items items x the row slices of nw 64-bit words at GW 32-bit words per thread
+BlockMap make_block_map(int nw, int GW, int n_items, unsigned &grid);
+// patch units of a launch over n_items items with GW words per thread and unit_threads threads per unit
+PatchArgs patch_args(const mp_ctx *c, int GW, int n_items, int unit_threads);
+// (re)builds the patch planes after mp_build_windows / mp_set_extra_rows changed the lists they mirror
+int ensure_patch_planes(mp_ctx *c);
+
 }  // namespace mp

@@ -12,7 +12,7 @@
 //   the planes on the fly (winwords.hpp) — round 1 kept a [W][Npad] u64 array of them (1 GB at the bench shard).
 //   excl / patch list, histogram tables and entries, labels: see windows.hip / unique.hip
 // Translation units: pack.hip (mp_load_msa), windows.hip (mp_build_windows), unique.hip (histograms),
-// eval.hip (candidate x sequence evaluation), dimer.hip (3'-end dimer scan, pair coverage), api.hip.
+// eval.hip (candidate x sequence evaluation), stats.hip (per-window statistics), dimer.hip (3'-end dimer scan, pair coverage), api.hip.
 // No MFMA anywhere: this is bit-mask work bounded by integer ALU / HBM.  gfx950 only.
 #pragma once
 
@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <utility>
 #include <chrono>
 #include <mutex>
 #include <unordered_map>
@@ -94,6 +95,18 @@ template <int NQ> struct NibT {
     }
 };
 typedef NibT<2> Nib;
+
+// The kernel form of a staged candidate set.  choose_eval_form (eval.hip) fills it as the last decision of mp_eval_upload — the only
+// place that reads the form switches and holds the size rules; a launch reads it and enqueues.  free_eval resets it.
+struct EvalForm {
+    enum Path : int8_t { None, RowsNarrow, RowsWide, Bits, BitsX } path = None;
+    int8_t bits_shape = 0;     // Bits: MP_EVAL_BITS 0..2
+    int8_t chain_shape = -1;   // Bits: index into the chain kernel / program shape tables; -1: no chain launch
+    bool use_prog = false;     // Bits: eval_prog_kernel (evalprog.hip) walks the chains, its programs written for chain_shape
+    int8_t x_shape = 0;        // BitsX: shape of eval_chain_x_kernel
+    int8_t row_variant = 0;    // RowsNarrow: kEvalVariants index
+    int8_t row_vmode = 0;      // Rows*: predicate specialisation 0, 1, 2 (2: the generic one)
+};
 
 }  // namespace mp
 
@@ -214,7 +227,7 @@ struct mp_ctx {
     std::vector<int32_t> h_cand_out;         // output slot of every padded candidate
     uint32_t *chain_prog = nullptr;          // fetch programs of the chain items (evalprog.hip), chains of up to 8 members only
     size_t chain_prog_n = 0;
-    int prog_shape = -1;                     // eval_prog_kernel shape the programs were written for (-1: eval_chain_kernel runs the chains)
+    mp::EvalForm form;                       // which kernels a launch of the staged set enqueues (chosen at upload)
     // sliding evaluation (evalslide.hip): plan of the staged chain items; slide_items = 0: the first-pass kernels run every item
     mp::SlideBand *slide_bands = nullptr;
     uint32_t *slide_iters = nullptr, *slide_recs = nullptr;
@@ -244,7 +257,6 @@ struct mp_ctx {
     double ev_ms = 0;
     std::vector<float> ev_samples, ev_last;     // per-launch durations since the last reset / as of the last mp_eval_timing call
     int ev_n = 0;
-    int eval_variant = 0;
     // host staging area of the streamed planning (mp_plan_create_streamed): kept for the context's life — handing 58 MB back to the
     // kernel and faulting them in again costs more than the copy that fills them
     uint8_t *h_stage = nullptr;              // host_map() memory

@@ -1,9 +1,8 @@
 // eval.hip — part of libmprime_hip.so: hand-written HIP (gfx950 / MI355X, wave64) behind the C ABI of
-// include/mprime.h.  Candidate x sequence coverage evaluation (mp_eval_*) and per-window statistics (mp_window_stats):
+// include/mprime.h.  Candidate x sequence coverage evaluation (mp_eval_*); the per-window statistics (4d) are in stats.hip:
 //   (4)  row-per-lane evaluation on the window words — eval_kernel (v > 3, MP_EVAL_MODE=rows); patch planes for the rest
 //   (4b) bit-sliced evaluation on the one-hot column planes, any 8 candidates — eval_bits_kernel
 //   (4c) bit-sliced evaluation of nested refinement chains — eval_chain_kernel (the benchmarked kernel)
-//   (4d) state_matrix / trans_matrix counts — window_stats_kernel
 //   per-sequence coverage masks — mask_rows_kernel
 #include "common.hpp"
 #include "winwords.hpp"
@@ -656,236 +655,6 @@ __global__ __launch_bounds__(kBlock) void eval_chain_long_kernel(const EvalChain
     }
 }
 
-// ----------------------------------------------------------------------------------------------
-// (4d) per-window base and nearest-neighbour counts (mp_window_stats; state_matrix / trans_matrix,
-// V20:541-577).  Same universe, same planes: freq[w][b][j] = popcount(valid_w & plane[col w+j][b]),
-// nn[w][j][a][b] = popcount(valid_w & plane[col w+j][a] & plane[col w+j+1][b]) over the plain rows, plus
-// the same pass over the windows' patch planes.  20 counters per position: a thread sums its GW words,
-// packs two 16-bit counts per register, six DPP adds give the wave total, lane 63 adds it to the block's
-// LDS table, the block adds its k x 20 totals to the global counters.
-// ----------------------------------------------------------------------------------------------
-struct StatsArgs {
-    const unsigned long long *cols;    // [n_cols][4][nw]
-    const unsigned long long *excl;    // [W][nw]
-    int nw, p0, k, v;
-    BlockMap map;                      // items = windows (window_stats_kernel) or groups of G windows (window_stats_group_kernel)
-    int n_win;
-    unsigned long long *freq;          // [W][4][k]
-    unsigned long long *nn;            // [W][k-1][16]
-    PatchArgs patch;
-};
-
-__device__ __forceinline__ void stats_flush(const StatsArgs &A, int win, const uint32_t (*s_cnt)[20]) {
-    for (int t = threadIdx.x; t < A.k * 20; t += kBlock) {
-        const int j = t / 20, q = t % 20;
-        const uint32_t val = s_cnt[j][q];
-        if (!val) continue;
-        if (q < 4) atomicAdd(&A.freq[((size_t)win * 4 + q) * A.k + j], (unsigned long long)val);
-        else if (j + 1 < A.k) atomicAdd(&A.nn[((size_t)win * (A.k - 1) + j) * 16 + (q - 4)], (unsigned long long)val);
-    }
-}
-
-template <int GW>
-__device__ __forceinline__ void stats_window_body(const StatsArgs &A, uint32_t (*s_cnt)[20]) {
-    const bool on_patch = (int)blockIdx.x < A.patch.n_blocks;
-    int slice, win;
-    if (on_patch) {
-        win = blockIdx.x / A.patch.per_item;
-        slice = blockIdx.x % A.patch.per_item;
-        if (win >= A.n_win) return;                   // (A.map counts window GROUPS in window_stats_group_kernel)
-    } else if (!map_block(A.map, blockIdx.x - A.patch.n_blocks, slice, win)) {
-        return;
-    }
-    const int word0 = (slice * kBlock + threadIdx.x) * GW;
-    const WordTile T = on_patch ? patch_tile(A.patch, win, word0) : column_tile(A.cols, A.excl, A.nw, A.p0, win, word0);
-    if (on_patch && (int)(slice * kBlock * GW) >= (int)T.stride) return;
-    for (int t = threadIdx.x; t < MP_MAX_K * 20; t += kBlock) (&s_cnt[0][0])[t] = 0;
-    __syncthreads();
-    const size_t nw32 = T.stride;
-    const bool live = T.live;
-    const uint32_t *Pw = T.planes;
-    uint32_t valid[GW], cur[4][GW], nxt[4][GW];
-#pragma unroll
-    for (int i = 0; i < GW; i++) {
-        valid[i] = live ? (T.mask[i] ^ T.mask_flip) : 0u;
-#pragma unroll
-        for (int b = 0; b < 4; b++) cur[b][i] = live ? (valid[i] & Pw[b * nw32 + i]) : 0u;
-    }
-#pragma unroll 1
-    for (int j = 0; j < A.k; j++) {
-        const bool more = j + 1 < A.k;
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-#pragma unroll
-            for (int i = 0; i < GW; i++) nxt[b][i] = (live && more) ? (valid[i] & Pw[((size_t)(j + 1) * 4 + b) * nw32 + i]) : 0u;
-        uint32_t cnt[20];
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            cnt[b] = 0;
-#pragma unroll
-            for (int i = 0; i < GW; i++) cnt[b] += __popc(cur[b][i]);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                cnt[4 + a * 4 + b] = 0;
-#pragma unroll
-                for (int i = 0; i < GW; i++) cnt[4 + a * 4 + b] += __popc(cur[a][i] & nxt[b][i]);
-            }
-        static_assert(64 * 32 * GW < 65536, "packed wave sums must fit 16 bits");
-        uint32_t tot[10];
-#pragma unroll
-        for (int q = 0; q < 10; q++) tot[q] = wave_sum_lane63(cnt[2 * q] | (cnt[2 * q + 1] << 16));
-        if ((threadIdx.x & 63) == 63) {
-#pragma unroll
-            for (int q = 0; q < 10; q++) {
-                if (tot[q] & 0xFFFFu) atomicAdd(&s_cnt[j][2 * q], tot[q] & 0xFFFFu);
-                if (tot[q] >> 16) atomicAdd(&s_cnt[j][2 * q + 1], tot[q] >> 16);
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-#pragma unroll
-            for (int i = 0; i < GW; i++) cur[b][i] = nxt[b][i];
-    }
-    __syncthreads();
-    stats_flush(A, win, s_cnt);
-}
-
-template <int GW>
-__global__ __launch_bounds__(kBlock) void window_stats_kernel(const StatsArgs A) {
-    __shared__ uint32_t s_cnt[MP_MAX_K][20];           // [position][4 base counts, then 16 pair counts (j, j+1)]
-    stats_window_body<GW>(A, s_cnt);
-}
-
-// Wave totals of 12 registers, TRANSPOSED (the reduction of evalslide.hip's commit: quad-masked DPP adds across the quads of a row, then
-// inside the quads, then v_permlane16/32_swap across the rows — a step that adds partner lanes also halves the registers): 31 instructions
-// instead of 12 x 6 DPP adds.  Afterwards lane L (L < 48, L % 4 == 0) holds the wave's total of register (L >> 4) * 4 + ((L >> 2) & 3).
-__device__ __forceinline__ uint32_t wave_sum12_transposed(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t x5, uint32_t x6,
-                                                          uint32_t x7, uint32_t x8, uint32_t x9, uint32_t x10, uint32_t x11) {
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_add_u32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_u32_dpp %2, %2, %2 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_u32_dpp %4, %4, %4 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_u32_dpp %6, %6, %6 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_u32_dpp %8, %8, %8 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_u32_dpp %10, %10, %10 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
-        "v_add_u32_dpp %0, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_u32_dpp %2, %3, %3 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_u32_dpp %4, %5, %5 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_u32_dpp %6, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_u32_dpp %8, %9, %9 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_u32_dpp %10, %11, %11 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_u32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_u32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_u32_dpp %8, %8, %8 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-        "v_add_u32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_u32_dpp %4, %6, %6 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_u32_dpp %8, %10, %10 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_u32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32_dpp %8, %8, %8 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32_dpp %4, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32_dpp %8, %8, %8 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(x8), "+v"(x9), "+v"(x10), "+v"(x11));
-    typedef unsigned int u32pair __attribute__((ext_vector_type(2)));
-    const u32pair s01 = __builtin_amdgcn_permlane16_swap(x0, x4, false, false);
-    const uint32_t a = s01.x + s01.y;
-    const u32pair s22 = __builtin_amdgcn_permlane16_swap(x8, x8, false, false);
-    const uint32_t b = s22.x + s22.y;
-    const u32pair h = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    return h.x + h.y;
-}
-
-// [r6] The same counts for G CONSECUTIVE windows per workgroup: window w uses column w + j at position j, so G neighbouring windows share all but
-// G - 1 of their k + G - 1 columns — the workgroup walks the columns once, every plane word is loaded once and counted under the validity words
-// of the (up to G) windows it belongs to.  The per-window kernel above re-reads every plane k times through L2 (9.4 GB at 10^6 x 1000, k = 18:
-// 2.27 ms with the vector ALUs 46 % busy); here (k + G - 1) / (G k) of that.  The arithmetic per (window, position) is the same 20 AND + popcount
-// pairs (the pair counts as one v_bitop3 a & b & valid each).  Plain rows only: the patch planes keep the kernel above (its patch blocks).
-template <int GW, int G>
-__global__ __launch_bounds__(kBlock) void window_stats_group_kernel(const StatsArgs A) {
-    // per window of the group and position: 10 words of two 16-bit counts (base counts 0-3, pair counts 4-19; a workgroup covers
-    // kBlock x 32 GW <= 32768 rows, so a field never carries) + 2 words of padding (the reduction works on 12 registers)
-    static_assert(kBlock * 32 * GW <= 32768, "two 16-bit counts per word");
-    __shared__ uint32_t s_grp[G][MP_MAX_K][12];
-    __shared__ uint32_t s_one[MP_MAX_K][20];
-    if ((int)blockIdx.x < A.patch.n_blocks) {                       // the patch planes: per window, as before
-        stats_window_body<GW>(A, s_one);
-        return;
-    }
-    int slice, grp;
-    if (!map_block(A.map, blockIdx.x - (unsigned)A.patch.n_blocks, slice, grp)) return;
-    const int w0 = grp * G, n_here = min(G, A.n_win - w0), k = A.k;
-    const int word0 = (slice * kBlock + (int)threadIdx.x) * GW, lane = (int)(threadIdx.x & 63);
-    const size_t nw32 = (size_t)A.nw * 2;
-    const bool live = word0 < (int)nw32;
-    for (int t = threadIdx.x; t < G * MP_MAX_K * 12; t += kBlock) (&s_grp[0][0][0])[t] = 0;
-    __syncthreads();
-    const uint32_t *Pw = reinterpret_cast<const uint32_t *>(A.cols) + ((size_t)(A.p0 + w0) * 4) * nw32 + word0;
-    const uint32_t *Ex = reinterpret_cast<const uint32_t *>(A.excl) + (size_t)w0 * nw32 + word0;
-    uint32_t valid[G][GW], cur[4][GW], nxt[4][GW];
-#pragma unroll
-    for (int g = 0; g < G; g++)
-#pragma unroll
-        for (int i = 0; i < GW; i++) valid[g][i] = (live && g < n_here) ? ~Ex[(size_t)g * nw32 + i] : 0u;
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-#pragma unroll
-        for (int i = 0; i < GW; i++) cur[b][i] = live ? Pw[b * nw32 + i] : 0u;
-    const int n_col = n_here + k - 1;
-    const bool adder = lane < 48 && (lane & 3) == 0;
-    const int my_word = (lane >> 4) * 4 + ((lane >> 2) & 3);
-#pragma unroll 1
-    for (int c = 0; c < n_col; c++) {
-        const bool more = c + 1 < n_col;
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-#pragma unroll
-            for (int i = 0; i < GW; i++) nxt[b][i] = (live && more) ? Pw[((size_t)(c + 1) * 4 + b) * nw32 + i] : 0u;
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const int j = c - g;                                   // the column's position in window w0 + g (wave-uniform)
-            if (g >= n_here || j < 0 || j >= k) continue;
-            uint32_t cnt[20];
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                cnt[b] = 0;
-#pragma unroll
-                for (int i = 0; i < GW; i++) cnt[b] += __popc(cur[b][i] & valid[g][i]);
-            }
-            // (at the window's last position nxt is the next window's column or zero: those pair counts are never read — stats_flush_packed)
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    cnt[4 + a * 4 + b] = 0;
-#pragma unroll
-                    for (int i = 0; i < GW; i++) cnt[4 + a * 4 + b] += __popc(__builtin_amdgcn_bitop3_b32(cur[a][i], nxt[b][i], valid[g][i], 0x80));
-                }
-            const uint32_t tot = wave_sum12_transposed(cnt[0] | (cnt[1] << 16), cnt[2] | (cnt[3] << 16), cnt[4] | (cnt[5] << 16), cnt[6] | (cnt[7] << 16),
-                                                       cnt[8] | (cnt[9] << 16), cnt[10] | (cnt[11] << 16), cnt[12] | (cnt[13] << 16), cnt[14] | (cnt[15] << 16),
-                                                       cnt[16] | (cnt[17] << 16), cnt[18] | (cnt[19] << 16), 0u, 0u);
-            if (adder) atomicAdd(&s_grp[g][j][my_word], tot);
-        }
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-#pragma unroll
-            for (int i = 0; i < GW; i++) cur[b][i] = nxt[b][i];
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < n_here * k * 20; t += kBlock) {
-        const int g = t / (k * 20), r = t % (k * 20), j = r / 20, q = r % 20, win = w0 + g;
-        const uint32_t val = (s_grp[g][j][q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
-        if (!val) continue;
-        if (q < 4) atomicAdd(&A.freq[((size_t)win * 4 + q) * k + j], (unsigned long long)val);
-        else if (j + 1 < k) atomicAdd(&A.nn[((size_t)win * (k - 1) + j) * 16 + (q - 4)], (unsigned long long)val);
-    }
-}
-
 // Per-sequence coverage masks (mp_eval_masks): thread = sequence, the wave's 64 "not covered" bits
 // go out as one 64-bit word per candidate straight from the ballot (blocks are 64-row aligned), so
 // there are no atomics; works on the window words, i.e. after edge-gap repair, for any v.
@@ -1004,28 +773,67 @@ const EvalVariant kEvalVariants[] = {
     EVAL_VARIANT("ballot/onehot", 1, false, 2),
 };
 constexpr int kNumEvalVariants = (int)(sizeof(kEvalVariants) / sizeof(kEvalVariants[0]));
+typedef void (*EvalWideFn)(const EvalArgsT<uint64_t>);
+const EvalWideFn kEvalWide[3] = {eval_kernel<kEvalCC, 0, 1, true, 2, uint64_t>, eval_kernel<kEvalCC, 1, 1, true, 2, uint64_t>,
+                                 eval_kernel<kEvalCC, 2, 1, true, 2, uint64_t>};      // fn[VMODE]
+// [v]: counter levels v + 1.  Symbol-table kernel: with / without the shared-position shortcut
+#define BITS_ROW(LV) {eval_bits_kernel<LV, 2, true, 1>, eval_bits_kernel<LV, 2, false, 1>}
+const EvalBitsFn kBitsFn[4][2] = {BITS_ROW(1), BITS_ROW(2), BITS_ROW(3), BITS_ROW(4)};
+#undef BITS_ROW
+// [v][EvalForm::chain_shape]: words per thread (kProgWords) x positions in flight.  Plane rows and patch planes are padded to multiples
+// of 8 words: 8 words per thread is the widest shape of eval_chain_kernel; shapes 9-13 — 16 words per thread, event planes parked in
+// LDS — exist in the program-driven kernel only
+#define CHAIN_ROW(K, LV) {K<LV, 2, 6>, K<LV, 2, 3>, K<LV, 2, 9>, K<LV, 4, 3>, K<LV, 4, 6>, K<LV, 1, 6>, K<LV, 8, 2>, K<LV, 8, 4>, K<LV, 8, 1>}
+#define CHAIN_TABLE(K) {CHAIN_ROW(K, 1), CHAIN_ROW(K, 2), CHAIN_ROW(K, 3), CHAIN_ROW(K, 4)}
+const EvalChainFn kChainFn[4][9] = CHAIN_TABLE(eval_chain_kernel), kChainLongFn[4][9] = CHAIN_TABLE(eval_chain_long_kernel);      // long: chains of more than 8 members
+#undef CHAIN_TABLE
+#undef CHAIN_ROW
 
+// padded patch words of window w (its patch-list and extra rows); the runs of kPatchRun rows that cover them are appended to `runs`
+int add_patch_runs(const mp_ctx *c, size_t w, std::vector<PatchRun> &runs) {
+    const int n = (c->h_patch_off[w + 1] - c->h_patch_off[w]) + (c->h_extra_off[w + 1] - c->h_extra_off[w]);
+    const int npw = ((n + 31) / 32 + 7) / 8 * 8;
+    for (int r0 = 0; r0 < npw * 32; r0 += kPatchRun) runs.push_back(PatchRun{(int32_t)w, r0});
+    return npw;
+}
 
+// A nested run as a chain item (ChainItem / ChainItemX): the symbols of its first member (`order`: most degenerate first) and one event
+// per base a later member loses — that base's column plane IS the increment
+template <typename Item, typename Sym>
+void fill_chain(Item &ch, const std::vector<int> &order, int k, Sym sym_at, std::vector<uint32_t> &events) {
+    ch.n_steps = (int32_t)order.size(); ch.ev0 = (int32_t)events.size();
+    for (int p = 0; p < k; p++) {
+        const uint32_t sy = sym_at(order[0], p);
+        ch.sym[p >> 3] |= sy << (4 * (p & 7));
+        const int nb = __builtin_popcount(sy);
+        (nb == 1 ? ch.pos1 : (nb == 2 ? ch.pos2 : ch.pos4)) |= (decltype(ch.pos1))1 << p;
+    }
+    for (size_t t = 1; t < order.size(); t++)
+        for (int p = 0; p < k; p++) {
+            const uint32_t lost = sym_at(order[t - 1], p) & ~sym_at(order[t], p);
+            for (uint32_t bit = 1; bit < 16; bit <<= 1)
+                if (lost & bit) events.push_back((uint32_t)p | (bit << 8) | ((uint32_t)t << 16));
+        }
+    ch.n_ev = (int32_t)events.size() - ch.ev0;
+}
 
-// (Re)builds the patch planes after mp_build_windows / mp_set_extra_rows changed the lists they mirror.
-int ensure_patch_planes(mp_ctx *c) {
+}  // namespace
+
+int mp::ensure_patch_planes(mp_ctx *c) {
     if (!c->pp_dirty) return MP_OK;
     dev_free(c, &c->pplanes, c->pp_words); dev_free(c, &c->pvalid, c->pv_words); dev_free(c, &c->pwin, (size_t)c->n_win);
-    c->pp_words = c->pv_words = 0;
-    c->max_npw = 0;
+    c->pp_words = c->pv_words = 0; c->max_npw = 0;
     const size_t W = (size_t)c->n_win;
     std::vector<PatchWin> pw(W);
     std::vector<PatchRun> runs;
     size_t poff = 0, voff = 0;
     for (size_t w = 0; w < W; w++) {
-        const int n = (c->h_patch_off[w + 1] - c->h_patch_off[w]) + (c->h_extra_off[w + 1] - c->h_extra_off[w]);
-        const int npw = ((n + 31) / 32 + 7) / 8 * 8;
+        const int npw = add_patch_runs(c, w, runs);
         if (poff + (size_t)c->k * 4 * npw > 0x7fffffffu) return fail(c, MP_ERR_NOMEM, "patch planes too large");
         pw[w] = PatchWin{(int32_t)poff, (int32_t)voff, npw};
         poff += (size_t)c->k * 4 * npw;
         voff += (size_t)npw;
         c->max_npw = std::max(c->max_npw, npw);
-        for (int r0 = 0; r0 < npw * 32; r0 += kPatchRun) runs.push_back(PatchRun{(int32_t)w, r0});
     }
     int rc;
     if ((rc = dev_alloc(c, &c->pwin, W))) return rc;
@@ -1057,7 +865,7 @@ int ensure_patch_planes(mp_ctx *c) {
 
 // The plain-slice planes of the patch-list rows (same sizes and offsets as the patch planes): built when the sliding evaluation first
 // needs them after the window lists changed.
-int ensure_plain_planes(mp_ctx *c) {
+static int ensure_plain_planes(mp_ctx *c) {
     int rc = ensure_patch_planes(c);
     if (rc) return rc;
     if (!c->qp_dirty) return MP_OK;
@@ -1066,11 +874,7 @@ int ensure_plain_planes(mp_ctx *c) {
     if ((rc = dev_alloc(c, &c->qplanes, c->pp_words))) return rc;
     if ((rc = dev_alloc(c, &c->qvalid, c->pv_words))) return rc;
     std::vector<PatchRun> runs;
-    for (size_t w = 0; w < (size_t)c->n_win; w++) {
-        const int n = (c->h_patch_off[w + 1] - c->h_patch_off[w]) + (c->h_extra_off[w + 1] - c->h_extra_off[w]);
-        const int npw = ((n + 31) / 32 + 7) / 8 * 8;
-        for (int r0 = 0; r0 < npw * 32; r0 += kPatchRun) runs.push_back(PatchRun{(int32_t)w, r0});
-    }
+    for (size_t w = 0; w < (size_t)c->n_win; w++) add_patch_runs(c, w, runs);
     PatchRun *d_runs = nullptr;
     if ((rc = dev_alloc(c, &d_runs, runs.size()))) return rc;
     HIPCK(c, hipMemcpyAsync(d_runs, runs.data(), sizeof(PatchRun) * runs.size(), hipMemcpyHostToDevice, c->stream));
@@ -1084,8 +888,7 @@ int ensure_plain_planes(mp_ctx *c) {
     return MP_OK;
 }
 
-// workgroups of a bit-sliced launch: n_items items x the row slices of nw 64-bit words at GW 32-bit words per thread (bitslice.hpp)
-BlockMap make_block_map(int nw, int GW, int n_items, unsigned &grid) {
+BlockMap mp::make_block_map(int nw, int GW, int n_items, unsigned &grid) {
     BlockMap m;
     m.ny = std::max(1, (2 * nw / GW + kBlock - 1) / kBlock);
     m.ny_pad = m.ny > 4 ? (m.ny + 7) / 8 * 8 : (m.ny > 2 ? 4 : m.ny);
@@ -1096,8 +899,7 @@ BlockMap make_block_map(int nw, int GW, int n_items, unsigned &grid) {
     return m;
 }
 
-// patch units of a launch over n_items items with GW words per thread and unit_threads threads per unit
-PatchArgs patch_args(const mp_ctx *c, int GW, int n_items, int unit_threads) {
+PatchArgs mp::patch_args(const mp_ctx *c, int GW, int n_items, int unit_threads) {
     PatchArgs pa{c->pplanes, c->pvalid, c->pwin, 0, 0, nullptr, nullptr, 0};
     static const bool skip = getenv("MP_EXPERIMENT_SKIP_PATCH") != nullptr;      // TIMING EXPERIMENTS ONLY (tools/): the counts come out wrong
     if (c->max_npw > 0 && n_items > 0 && !skip) {
@@ -1107,8 +909,6 @@ PatchArgs patch_args(const mp_ctx *c, int GW, int n_items, int unit_threads) {
     }
     return pa;
 }
-
-}  // namespace
 
 // [r6] The chain items of eval_chain_x_kernel (evalx.hpp) for a staged candidate set of primers of 32..63 bases or of v = 4, 5: every
 // maximal run of at most 8 consecutive candidates of a window that is nested in one direction (a refinement chain read either way) is
@@ -1147,20 +947,8 @@ static int upload_x(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t 
             if ((dir & 2) == 0) for (int ci = e - 1; ci >= b; ci--) order.push_back(ci);      // ascending run: most degenerate member last
             else for (int ci = b; ci < e; ci++) order.push_back(ci);
             ChainItemX ch{};
-            ch.win = w; ch.cand0 = (int32_t)co.size(); ch.n_steps = (int32_t)order.size(); ch.ev0 = (int32_t)events.size();
-            for (int p = 0; p < k; p++) {
-                const uint32_t sy = sym_at(order[0], p);
-                ch.sym[p >> 3] |= sy << (4 * (p & 7));
-                const int nb = __builtin_popcount(sy);
-                (nb == 1 ? ch.pos1 : (nb == 2 ? ch.pos2 : ch.pos4)) |= 1ull << p;
-            }
-            for (size_t t = 1; t < order.size(); t++)
-                for (int p = 0; p < k; p++) {
-                    const uint32_t lost = sym_at(order[t - 1], p) & ~sym_at(order[t], p);
-                    for (uint32_t bit = 1; bit < 16; bit <<= 1)
-                        if (lost & bit) events.push_back((uint32_t)p | (bit << 8) | ((uint32_t)t << 16));
-                }
-            ch.n_ev = (int32_t)events.size() - ch.ev0;
+            ch.win = w; ch.cand0 = (int32_t)co.size();
+            fill_chain(ch, order, k, sym_at, events);
             items.push_back(ch);
             for (int t = 0; t < kEvalCC; t++) co.push_back(t < (int)order.size() ? order[(size_t)t] : -1);
             b = e;
@@ -1185,21 +973,136 @@ static int upload_x(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t 
 typedef void (*EvalXFn)(const EvalXArgs);
 static int launch_eval_x(mp_ctx *c, unsigned long long *out) {
     { int rc = ensure_patch_planes(c); if (rc) return rc; }
-    const int nw = c->n_pad / 64, nw32 = 2 * nw;
     // words per thread x positions in flight by depth (as eval_chain_kernel chooses them); five and six counter levels: at most 4 words
 #define X_ROW(LV) {eval_chain_x_kernel<LV, 1, 6>, eval_chain_x_kernel<LV, 2, 6>, eval_chain_x_kernel<LV, 4, 3>, eval_chain_x_kernel<LV, (LV <= 4 ? 8 : 4), (LV <= 4 ? 2 : 3)>}
     static const EvalXFn fn[6][4] = {X_ROW(1), X_ROW(2), X_ROW(3), X_ROW(4), X_ROW(5), X_ROW(6)};
 #undef X_ROW
-    int shape = nw32 >= 4 * kBlock ? 3 : (nw32 >= 2 * kBlock ? 2 : (nw32 >= kBlock ? 1 : 0));
-    if (const char *e = getenv("MP_EVAL_X_SHAPE")) { const int sh = atoi(e); if (sh >= 0 && sh < 4) shape = sh; }
-    static const int gw_of[4] = {1, 2, 4, 8};
-    const int GW = shape == 3 && c->v >= 4 ? 4 : gw_of[shape];
+    const int nw = c->n_pad / 64, shape = c->form.x_shape, GW = shape == 3 && c->v >= 4 ? 4 : 1 << shape;
     unsigned grid;
     const BlockMap bm = make_block_map(nw, GW, c->x_n, grid);
     EvalXArgs xa{c->cols, c->excl, nw, c->p0, c->k, c->v, reinterpret_cast<const ChainItemX *>(c->x_items), c->x_events, c->x_cand_out, c->sF, c->sR, out, bm,
                  patch_args(c, GW, c->x_n, 64)};
     hipLaunchKernelGGL(fn[c->v][shape], dim3(grid + (unsigned)xa.patch.n_blocks), dim3(kBlock), 0, c->stream, xa);
     return MP_OK;
+}
+
+// The kernel form of the set mp_eval_upload has just staged (mp_ctx::form): the only reader of the form switches, the only holder of the
+// size rules.  All it looks at changes only with a new mp_build_windows / mp_load_msa, which drops the staged set; a switch changed after
+// the upload waits for the next one.  nw32 = n_pad / 32 (32-bit words of a plane row), kBlock = 256.
+//   path    MP_EVAL_MODE=rows: RowsWide (k > 31) / RowsNarrow.  Else v <= 3 and k <= 31: Bits; x items staged (upload_x): BitsX; else rows
+//   Bits    bits_shape = MP_EVAL_BITS in 0..2, else 0.  1: symbol-table kernel on every item, without the shared-position shortcut; 2: with
+//           it; 0: on the items that are no chains, and a chain launch (chain_shape >= 0) for those that are:
+//           chains of <= kEvalCC members, none taken by the sliding plan, and MP_EVAL_PROG=1: eval_prog_kernel, shape MP_EVAL_CHAIN in
+//             0..kProgShapes-1, else (or unset) 7;  the same and MP_EVAL_PROG unset: eval_prog_kernel from n_pad >= 393216, shape 11
+//             whatever MP_EVAL_CHAIN says (profiles/r03_prog_keep.txt: faster where the planes no longer come out of L2, slower below)
+//           otherwise eval_chain_kernel, shape MP_EVAL_CHAIN in 0..8, else 0; unset: 7 (8 words x 4 positions) from nw32 >= 4 kBlock,
+//             3 (4 x 3) from 2 kBlock, 0 (2 x 6) from kBlock, else 5 (1 x 6): a block that covers more sequences spreads its fixed costs
+//   BitsX   x_shape = MP_EVAL_X_SHAPE in 0..3, else (or unset) 3, 2, 1 from nw32 >= 4 kBlock, 2 kBlock, kBlock, else 0
+//   Rows*   row_vmode 0, 1, 2 for v = 0, 1, more; MP_EVAL_GENERIC_V: 2 (RowsWide: for v = 1 only).  RowsNarrow: row_variant =
+//           MP_EVAL_VARIANT in 0..kNumEvalVariants-1, else 0
+static void choose_eval_form(mp_ctx *c) {
+    const char *mode_e = getenv("MP_EVAL_MODE"), *bits_e = getenv("MP_EVAL_BITS"), *chain_e = getenv("MP_EVAL_CHAIN"), *prog_e = getenv("MP_EVAL_PROG"),
+               *x_e = getenv("MP_EVAL_X_SHAPE"), *variant_e = getenv("MP_EVAL_VARIANT");
+    const bool generic_v = getenv("MP_EVAL_GENERIC_V") != nullptr, rows = mode_e && !strcmp(mode_e, "rows");
+    auto pick = [](const char *e, int hi, int unset, int bad) { if (!e) return unset; const int x = atoi(e); return x >= 0 && x <= hi ? x : bad; };
+    const int nw32 = 2 * (c->n_pad / 64), vmode = c->v == 0 ? 0 : (c->v == 1 ? 1 : 2);
+    EvalForm f;
+    if (!rows && c->v <= 3 && !c->wide) {                     // (the bit-sliced kernels hold 32 positions per item and four counter levels)
+        f.path = EvalForm::Bits; f.bits_shape = (int8_t)pick(bits_e, 2, 0, 0);
+        if (f.bits_shape == 0 && c->n_chain) {
+            f.use_prog = c->max_steps <= kEvalCC && c->slide_items == 0 && (prog_e ? atoi(prog_e) == 1 : c->n_pad >= 393216);
+            if (f.use_prog) f.chain_shape = (int8_t)(prog_e ? pick(chain_e, kProgShapes - 1, 7, 7) : 11);
+            else f.chain_shape = (int8_t)pick(chain_e, 8, nw32 >= 4 * kBlock ? 7 : (nw32 >= 2 * kBlock ? 3 : (nw32 >= kBlock ? 0 : 5)), 0);
+        }
+    } else if (!rows && c->x_n > 0) {                          // [r6] 32..63 positions / v = 4, 5: eval_chain_x_kernel
+        f.path = EvalForm::BitsX;
+        const int by_size = nw32 >= 4 * kBlock ? 3 : (nw32 >= 2 * kBlock ? 2 : (nw32 >= kBlock ? 1 : 0));
+        f.x_shape = (int8_t)pick(x_e, 3, by_size, by_size);
+    } else if (c->wide) {
+        f.path = EvalForm::RowsWide; f.row_vmode = (int8_t)(vmode == 1 && generic_v ? 2 : vmode);
+    } else {
+        f.path = EvalForm::RowsNarrow; f.row_vmode = (int8_t)(generic_v ? 2 : vmode);
+        f.row_variant = (int8_t)pick(variant_e, kNumEvalVariants - 1, 0, 0);
+    }
+    c->form = f;
+}
+
+// The chain items of a bit-sliced step (form.chain_shape >= 0): sliding, program-driven or first-pass kernel.  `clear` (n_clear counters, may
+// be null) is the rotating form's side job: the first kernel of the step that can take it does, and leaves null behind for the others
+static int launch_chains(mp_ctx *c, unsigned long long *out, unsigned long long *&clear, uint32_t n_clear) {
+    const int nw = c->n_pad / 64, cshape = c->form.chain_shape, gw = kProgWords[cshape];
+    unsigned grid;
+    const BlockMap bm = make_block_map(nw, gw, c->n_chain, grid);
+    EvalChainArgs ca{c->cols, c->excl, nw, c->p0, c->k, c->v, c->chain_items, c->chain_events, c->cand_out, (uint32_t)c->sF, (uint32_t)c->sR,
+                     out, bm, patch_args(c, gw, c->n_chain, 64), nullptr, 0};
+    if (c->form.use_prog) return launch_eval_prog(c, cshape, bm, ca.patch, grid, out);      // evalprog.hip: same arithmetic and block map
+    if (c->slide_items == 0) {
+        ca.clear = std::exchange(clear, nullptr); ca.n_clear = n_clear;
+        hipLaunchKernelGGL((c->max_steps > kEvalCC ? kChainLongFn : kChainFn)[c->v][cshape], dim3(grid + (unsigned)ca.patch.n_blocks), dim3(kBlock), 0,
+                           c->stream, ca);
+        return MP_OK;
+    }
+    // sliding evaluation: the patch planes of ALL chain items and the column planes of the items the plan left out run on the first-pass
+    // kernel, the rest slides (the sliding kernel counts every row of a window as a plain column slice: the patch planes add the patch-list
+    // rows' real k-mers, their plain-slice planes take the plain counts back — the exclusion words are not read at all)
+    EvalChainArgs pa2 = ca;
+    int patch_blocks = 0, pgw = 8, rc;
+    if (ca.patch.n_blocks) {
+        if ((rc = ensure_plain_planes(c))) return rc;
+        // chains of more than 8 members: the long-chain kernel, a launch of its own, units of 8 words per thread; else the
+        // units are the tail of the sliding launch, one word per lane (chainbody.hpp: eval_patch_wave)
+        const bool long_chains = c->max_steps > kEvalCC;
+        pgw = long_chains || c->max_npw > 64 ? 8 : 1;
+        pa2.patch = patch_args(c, pgw, c->n_chain, 64);
+        const PatchArgs neg = patch_args(c, pgw, c->slide_items, 64);
+        pa2.patch.qplanes = c->qplanes; pa2.patch.qvalid = c->qvalid; pa2.patch.neg_blocks = neg.n_blocks;
+        pa2.neg_items = c->chain_slid; pa2.n_neg = c->slide_items;
+        patch_blocks = pa2.patch.n_blocks + neg.n_blocks;
+        if (long_chains) {
+            hipLaunchKernelGGL(kChainLongFn[c->v][7], dim3((unsigned)patch_blocks), dim3(kBlock), 0, c->stream, pa2);
+            patch_blocks = 0;
+        }
+    }
+    if (c->n_rest) {
+        unsigned rgrid;
+        const BlockMap rbm = make_block_map(nw, gw, c->n_rest, rgrid);
+        EvalChainArgs ra = ca;
+        ra.items = c->chain_rest; ra.map = rbm; ra.patch = PatchArgs{nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0};
+        hipLaunchKernelGGL((c->rest_max_steps > kEvalCC ? kChainLongFn : kChainFn)[c->v][cshape], dim3(rgrid), dim3(kBlock), 0, c->stream, ra);
+    }
+    return launch_eval_slide(c, out, patch_blocks ? &pa2 : nullptr, patch_blocks, pgw, std::exchange(clear, nullptr), n_clear);
+}
+
+// bit-sliced pass over the column planes and over the windows' patch planes
+static int launch_bits(mp_ctx *c, unsigned long long *out, unsigned long long *&clear, uint32_t n_clear) {
+    int rc = ensure_patch_planes(c);
+    if (rc) return rc;
+    const int shape = c->form.bits_shape, nw = c->n_pad / 64;
+    if (c->form.chain_shape >= 0 && (rc = launch_chains(c, out, clear, n_clear))) return rc;
+    const int n_tab = shape == 0 ? c->n_table : c->n_items;
+    if (n_tab) {
+        unsigned grid;
+        const BlockMap bm = make_block_map(nw, 2, n_tab, grid);
+        EvalBitsArgs ba{c->cols, c->excl, nw, c->p0, c->k, c->v, c->items, c->cand_symT, c->cand_out, (uint32_t)c->sF, (uint32_t)c->sR,
+                        out, bm, c->cand_diff, shape == 0 ? c->table_ids : (const int32_t *)nullptr,
+                        patch_args(c, 2, n_tab, 64), nullptr, nullptr, c->n_rows, std::exchange(clear, nullptr), n_clear};
+        hipLaunchKernelGGL(kBitsFn[c->v][shape == 1 ? 1 : 0], dim3(grid + (unsigned)ba.patch.n_blocks), dim3(kBlock), 0, c->stream, ba);
+    }
+    return MP_OK;
+}
+
+// row-per-lane kernel on the window words: W = uint32_t (k <= 31, kEvalVariants) or uint64_t (primers of 32..63 bases, kEvalWide)
+template <typename W>
+static void launch_rows(mp_ctx *c, unsigned long long *out, void (*fn)(const EvalArgsT<W>)) {
+    // enough blocks to fill 256 CUs several times over, each with at least 1024 sequences
+    const int max_split = (c->n_pad + 1023) / 1024, want = (4096 + c->n_items - 1) / c->n_items;
+    int split = std::max(1, std::min(max_split, want));
+    const int rows = ((c->n_pad + split - 1) / split + 1023) / 1024 * 1024;
+    split = (c->n_pad + rows - 1) / rows;
+    const EvalArgsT<W> ea{msa_args(c), c->p0, c->n_pad, c->k, c->items, reinterpret_cast<const CandN<W> *>(c->cand_n), c->cand_out,
+                          c->n_extra ? c->extra_off : (const int32_t *)nullptr, reinterpret_cast<const W *>(c->extra_words), (W)c->sF, (W)c->sR,
+                          c->v, kmask_of<W>(c->k), rows, out};
+    hipLaunchKernelGGL(fn, dim3((unsigned)c->n_items, (unsigned)split), dim3(kBlock), 0, c->stream, ea);
 }
 
 extern "C" {
@@ -1246,7 +1149,9 @@ static int upload_wide(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8
     HIPCK(c, hipMemcpy(c->items, items.data(), sizeof(EvalItem) * items.size(), hipMemcpyHostToDevice));
     HIPCK(c, hipMemcpy(c->cand_n, cn.data(), sizeof(CandN<uint64_t>) * cn.size(), hipMemcpyHostToDevice));
     HIPCK(c, hipMemcpy(c->cand_out, co.data(), sizeof(int32_t) * co.size(), hipMemcpyHostToDevice));
-    return upload_x(c, n_cand, cw, codes);           // [r6] the bit-sliced chain items beside the row-per-lane arrays
+    if ((rc = upload_x(c, n_cand, cw, codes))) return rc;      // [r6] the bit-sliced chain items beside the row-per-lane arrays
+    choose_eval_form(c);
+    return MP_OK;
 }
 
 int mp_eval_upload(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *codes, uint64_t sF64, uint64_t sR64) {
@@ -1278,7 +1183,6 @@ int mp_eval_upload(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *
                 if (sym_at(ci, p) != sym_at(b, p)) dm |= 1u << p;
         return dm;
     };
-    // one item = up to 8 slots; `order` lists its candidates (for a nested run: most degenerate first)
     // 8 output slots (one EvalItem) from `order[g0 .. g0+8)`; `order` lists candidates (for a nested run: most degenerate first)
     auto emit_slots = [&](int w, const std::vector<int> &order, int g0) {
         const int n = std::min(kEvalCC, (int)order.size() - g0);
@@ -1310,20 +1214,9 @@ int mp_eval_upload(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *
     auto emit = [&](int w, const std::vector<int> &order, bool nested) {
         const int n = (int)order.size();
         if (nested) {
-            ChainItem ch{w, (int32_t)cn.size(), n, (int32_t)events.size(), 0, {0u, 0u, 0u, 0u}, 0u, 0u, 0u};
-            for (int p = 0; p < k; p++) {
-                const uint32_t sy = sym_at(order[0], p);
-                ch.sym[p >> 3] |= sy << (4 * (p & 7));
-                const int nb = __builtin_popcount(sy);
-                (nb == 1 ? ch.pos1 : (nb == 2 ? ch.pos2 : ch.pos4)) |= 1u << p;
-            }
-            for (int t = 1; t < n; t++)
-                for (int p = 0; p < k; p++) {
-                    const uint32_t lost = sym_at(order[t - 1], p) & ~sym_at(order[t], p);
-                    for (uint32_t bit = 1; bit < 16; bit <<= 1)      // one event per lost base: its column plane IS the increment
-                        if (lost & bit) events.push_back((uint32_t)p | (bit << 8) | ((uint32_t)t << 16));
-                }
-            ch.n_ev = (int32_t)events.size() - ch.ev0;
+            ChainItem ch{};
+            ch.win = w; ch.cand0 = (int32_t)cn.size();
+            fill_chain(ch, order, k, sym_at, events);
             chains.push_back(ch);
             for (int g0 = 0; g0 < n; g0 += kEvalCC) emit_slots(w, order, g0);
         } else {
@@ -1401,28 +1294,9 @@ int mp_eval_upload(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *
     c->h_chains = chains;
     c->h_events = events;
     c->h_cand_out = co;
-    // Which kernel walks the chains.  eval_prog_kernel (evalprog.hip: host-written fetch programs, buffer loads, event planes parked
-    // in LDS) is faster from about 400 000 rows up, where the planes no longer come out of L2 (shape 11: 1.122 vs 1.193 ms / 10 steps at
-    // 524 288 rows, 0.217-0.223 vs 0.240-0.242 ms at 1 048 576; slower below: 0.0549 vs 0.0524 ms at 262 144 —
-    // profiles/r03_prog_keep.txt); eval_chain_kernel otherwise.  MP_EVAL_PROG=1 / 0 forces one of them, MP_EVAL_CHAIN the shape.
     // The sliding kernel (evalslide.hip) takes the chain items it can (all of them in a refinement run); what it leaves out stays with
-    // the first-pass kernel below.  MP_EVAL_SLIDE=0 / 1 forbids / forces it.
+    // the first-pass kernel.  MP_EVAL_SLIDE=0 / 1 forbids / forces it.
     if (c->n_chain && (rc = upload_eval_slide(c, chains, events, co))) return rc;
-    c->prog_shape = -1;
-    if (c->n_chain && c->max_steps <= kEvalCC && c->slide_items == 0) {
-        const char *pe = getenv("MP_EVAL_PROG");
-        if (pe ? atoi(pe) == 1 : c->n_pad >= 393216) {
-            c->prog_shape = pe ? 7 : 11;
-            if (const char *e = getenv("MP_EVAL_CHAIN")) { const int sh = atoi(e); if (pe && sh >= 0 && sh < kProgShapes) c->prog_shape = sh; }
-        }
-    }
-    if (c->prog_shape >= 0) {
-        std::vector<uint32_t> prog;                // the programs carry the LDS slots of the shape that will run them
-        build_eval_programs(chains, events, co, k, sF, sR, kProgKeep[c->prog_shape], prog);
-        if ((rc = dev_alloc(c, &c->chain_prog, prog.size()))) return rc;
-        c->chain_prog_n = prog.size();
-        HIPCK(c, hipMemcpy(c->chain_prog, prog.data(), sizeof(uint32_t) * prog.size(), hipMemcpyHostToDevice));
-    }
     if (c->n_chain) {
         if ((rc = dev_alloc(c, &c->chain_items, chains.size()))) return rc;
         HIPCK(c, hipMemcpy(c->chain_items, chains.data(), sizeof(ChainItem) * chains.size(), hipMemcpyHostToDevice));
@@ -1436,12 +1310,21 @@ int mp_eval_upload(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *
     HIPCK(c, hipMemcpy(c->items, items.data(), sizeof(EvalItem) * items.size(), hipMemcpyHostToDevice));
     HIPCK(c, hipMemcpy(c->cand_n, cn.data(), sizeof(uint4) * cn.size(), hipMemcpyHostToDevice));
     HIPCK(c, hipMemcpy(c->cand_out, co.data(), sizeof(int32_t) * co.size(), hipMemcpyHostToDevice));
-    if (c->v > 3) return upload_x(c, n_cand, cw, codes);     // [r6] v = 4, 5: the four-level kernels above do not count that far
+    if (c->v > 3 && (rc = upload_x(c, n_cand, cw, codes))) return rc;     // [r6] v = 4, 5: the four-level kernels above do not count that far
+    choose_eval_form(c);
+    if (c->form.use_prog) {                        // the programs carry the LDS slots of the shape that will run them
+        std::vector<uint32_t> prog;
+        build_eval_programs(chains, events, co, k, sF, sR, kProgKeep[c->form.chain_shape], prog);
+        if ((rc = dev_alloc(c, &c->chain_prog, prog.size()))) return rc;
+        c->chain_prog_n = prog.size();
+        HIPCK(c, hipMemcpy(c->chain_prog, prog.data(), sizeof(uint32_t) * prog.size(), hipMemcpyHostToDevice));
+    }
     return MP_OK;
 }
 
 // zero_out: the launch clears device_out itself first (mp_eval_launch).  Otherwise the caller vouches for a zeroed device_out
 // (mp_eval_launch_rotating) and `device_clear`, if given, is zeroed by the first evaluation kernel of the step inside its own grid.
+// Which kernels run was decided when the set was staged (mp_ctx::form): nothing here reads the environment but the timing switch.
 static int eval_launch_impl(mp_ctx *c, int64_t *device_out, int64_t *device_clear, bool zero_out) {
     if (!c) return MP_ERR_ARG;
     if (!c->excl) return fail(c, MP_ERR_ARG, "no windows built");
@@ -1463,16 +1346,7 @@ static int eval_launch_impl(mp_ctx *c, int64_t *device_out, int64_t *device_clea
         return fail(c, MP_ERR_ARG, "mp_eval_launch_rotating: this block was cleared for %zu counters by the launch before, the staged set needs %zu",
                     c->rot_cleared, n_counters);
     if (!zero_out) { c->rot_block = device_clear; c->rot_cleared = device_clear ? n_counters : 0; }
-    // the rotating form's side job goes to the first kernel of the step that can take it (a kernel that cannot leaves it pending)
-    unsigned long long *pending_clear = reinterpret_cast<unsigned long long *>(device_clear);
-    auto take_clear = [&]() { unsigned long long *p = pending_clear; pending_clear = nullptr; return p; };
-    const uint32_t n_clear = (uint32_t)n_counters;
-    // enough blocks to fill 256 CUs several times over, each with at least 1024 sequences
-    int max_split = (c->n_pad + 1023) / 1024;
-    int want = (4096 + c->n_items - 1) / c->n_items;
-    int split = std::max(1, std::min(max_split, want));
-    int rows = ((c->n_pad + split - 1) / split + 1023) / 1024 * 1024;
-    split = (c->n_pad + rows - 1) / rows;
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(device_out), *pending_clear = reinterpret_cast<unsigned long long *>(device_clear);
     // HIP-event timing of the launch (mp_eval_timing).  An event pair idles the stream for ~6 us, so
     // MP_EVAL_TIMING_EVERY=n times every n-th launch only, counted from the last timing reset (0: none); default: all.
     int every = 1;
@@ -1484,129 +1358,17 @@ static int eval_launch_impl(mp_ctx *c, int64_t *device_out, int64_t *device_clea
         else { HIPCK(c, hipEventCreate(&ev.first)); HIPCK(c, hipEventCreate(&ev.second)); }
         HIPCK(c, hipEventRecord(ev.first, c->stream));
     }
-    const char *mode_env = getenv("MP_EVAL_MODE");
-    const bool bits = c->v <= 3 && !c->wide && !(mode_env && !strcmp(mode_env, "rows"));      // (the bit-sliced kernels hold 32 positions per item)
-    const bool xbits = !bits && c->x_n > 0 && !(mode_env && !strcmp(mode_env, "rows"));       // [r6] 32..63 positions / v = 4, 5: eval_chain_x_kernel
-    const int vmode = c->v == 0 ? 0 : (c->v == 1 ? 1 : 2);     // predicate specialisation of the row-per-lane code
-    if (xbits) {
-        const int rc = launch_eval_x(c, (unsigned long long *)device_out);
-        if (rc) return rc;
-    } else if (bits) {
-        // bit-sliced pass over the column planes and over the windows' patch planes
-        // MP_EVAL_BITS: 0 (default) = nested-chain kernel on the nested items + symbol-table kernel (with the shared-
-        // position shortcut) on the others; 1 = symbol-table kernel on every item, no shortcut; 2 = the same with it
-        int shape = 0;
-        if (const char *e = getenv("MP_EVAL_BITS")) { shape = atoi(e); if (shape < 0 || shape > 2) shape = 0; }
-        const int nw = c->n_pad / 64;
-        auto block_map = [&](int GW, int n_items, unsigned &grid) { return make_block_map(nw, GW, n_items, grid); };
-        { int rc = ensure_patch_planes(c); if (rc) return rc; }
-        static const EvalBitsFn tfn[4][2] = {{eval_bits_kernel<1, 2, true, 1>, eval_bits_kernel<1, 2, false, 1>},
-                                             {eval_bits_kernel<2, 2, true, 1>, eval_bits_kernel<2, 2, false, 1>},
-                                             {eval_bits_kernel<3, 2, true, 1>, eval_bits_kernel<3, 2, false, 1>},
-                                             {eval_bits_kernel<4, 2, true, 1>, eval_bits_kernel<4, 2, false, 1>}};
-        if (shape == 0 && c->n_chain) {
-            // words per thread x positions in flight: the more sequences a block covers, the further its fixed costs
-            // (24 popcount totals, item and event fetches) are spread — 8 x 4 from 32768 sequences up (half a block of
-            // threads at that size), 4 x 3 from 16384, else 2 x 6 / 1 x 6.  MP_EVAL_CHAIN overrides (tools/variant_bench.py).
-            const int nw32 = 2 * nw;
-            int cshape = nw32 >= 4 * kBlock ? 7 : (nw32 >= 2 * kBlock ? 3 : (nw32 >= kBlock ? 0 : 5));
-            const bool use_prog = c->chain_prog && c->prog_shape >= 0;
-            if (use_prog) cshape = c->prog_shape;
-            else if (const char *e = getenv("MP_EVAL_CHAIN")) { cshape = atoi(e); if (cshape < 0 || cshape > 8) cshape = 0; }
-            // (plane rows and patch planes are padded to multiples of 8 words: 8 words per thread is the widest shape of
-            // eval_chain_kernel; shapes 9-12 — 16 words per thread, event planes parked in LDS — exist in the program-driven kernel only)
-            const int *cgw = kProgWords;
-#define CHAIN_ROW(LV) {eval_chain_kernel<LV, 2, 6>, eval_chain_kernel<LV, 2, 3>, eval_chain_kernel<LV, 2, 9>, eval_chain_kernel<LV, 4, 3>, \
-                       eval_chain_kernel<LV, 4, 6>, eval_chain_kernel<LV, 1, 6>, eval_chain_kernel<LV, 8, 2>, eval_chain_kernel<LV, 8, 4>, \
-                       eval_chain_kernel<LV, 8, 1>}
-            static const EvalChainFn cfn[4][9] = {CHAIN_ROW(1), CHAIN_ROW(2), CHAIN_ROW(3), CHAIN_ROW(4)};
-#undef CHAIN_ROW
-#define CHAIN_ROW(LV) {eval_chain_long_kernel<LV, 2, 6>, eval_chain_long_kernel<LV, 2, 3>, eval_chain_long_kernel<LV, 2, 9>, \
-                       eval_chain_long_kernel<LV, 4, 3>, eval_chain_long_kernel<LV, 4, 6>, eval_chain_long_kernel<LV, 1, 6>, \
-                       eval_chain_long_kernel<LV, 8, 2>, eval_chain_long_kernel<LV, 8, 4>, eval_chain_long_kernel<LV, 8, 1>}
-            static const EvalChainFn lfn[4][9] = {CHAIN_ROW(1), CHAIN_ROW(2), CHAIN_ROW(3), CHAIN_ROW(4)};
-#undef CHAIN_ROW
-            unsigned grid;
-            const BlockMap bm = block_map(cgw[cshape], c->n_chain, grid);
-            EvalChainArgs ca{c->cols, c->excl, nw, c->p0, c->k, c->v, c->chain_items, c->chain_events, c->cand_out, (uint32_t)c->sF, (uint32_t)c->sR,
-                             (unsigned long long *)device_out, bm, patch_args(c, cgw[cshape], c->n_chain, 64), nullptr, 0};
-            if (c->slide_items > 0) {
-                // sliding evaluation: the patch planes of ALL chain items and the column planes of the items the plan left out run on
-                // the first-pass kernel, the rest slides
-                // (the sliding kernel counts every row of a window as a plain column slice: the patch planes add the patch-list rows'
-                // real k-mers, their plain-slice planes take the plain counts back — the exclusion words are not read at all)
-                EvalChainArgs pa2 = ca;
-                int patch_blocks = 0, pgw = 8;
-                if (ca.patch.n_blocks) {
-                    { int rc = ensure_plain_planes(c); if (rc) return rc; }
-                    // chains of more than 8 members: the long-chain kernel, a launch of its own, units of 8 words per thread; else the
-                    // units are the tail of the sliding launch, one word per lane (chainbody.hpp: eval_patch_wave)
-                    const bool long_chains = c->max_steps > kEvalCC;
-                    pgw = long_chains || c->max_npw > 64 ? 8 : 1;
-                    pa2.patch = patch_args(c, pgw, c->n_chain, 64);
-                    const PatchArgs neg = patch_args(c, pgw, c->slide_items, 64);
-                    pa2.patch.qplanes = c->qplanes; pa2.patch.qvalid = c->qvalid; pa2.patch.neg_blocks = neg.n_blocks;
-                    pa2.neg_items = c->chain_slid; pa2.n_neg = c->slide_items;
-                    patch_blocks = pa2.patch.n_blocks + neg.n_blocks;
-                    if (long_chains) {
-                        hipLaunchKernelGGL(lfn[c->v][7], dim3((unsigned)patch_blocks), dim3(kBlock), 0, c->stream, pa2);
-                        patch_blocks = 0;
-                    }
-                }
-                if (c->n_rest) {
-                    unsigned rgrid;
-                    const BlockMap rbm = block_map(cgw[cshape], c->n_rest, rgrid);
-                    PatchArgs none{nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0};
-                    EvalChainArgs ra{c->cols, c->excl, nw, c->p0, c->k, c->v, c->chain_rest, c->chain_events, c->cand_out, (uint32_t)c->sF, (uint32_t)c->sR,
-                                     (unsigned long long *)device_out, rbm, none, nullptr, 0};
-                    hipLaunchKernelGGL((c->rest_max_steps > kEvalCC ? lfn : cfn)[c->v][cshape], dim3(rgrid), dim3(kBlock), 0, c->stream, ra);
-                }
-                int rc = launch_eval_slide(c, (unsigned long long *)device_out, patch_blocks ? &pa2 : nullptr, patch_blocks, pgw, take_clear(), n_clear);
-                if (rc) return rc;
-            } else {
-            if (use_prog) {
-                // program-driven kernel (evalprog.hip): same arithmetic and block map (chosen at upload time, see there)
-                int rc = launch_eval_prog(c, cshape, bm, ca.patch, grid, (unsigned long long *)device_out);
-                if (rc) return rc;
-            } else {
-                ca.clear = take_clear(); ca.n_clear = n_clear;
-                hipLaunchKernelGGL((c->max_steps > kEvalCC ? lfn : cfn)[c->v][cshape], dim3(grid + (unsigned)ca.patch.n_blocks), dim3(kBlock), 0,
-                                   c->stream, ca);
-            }
-            }
-        }
-        const int n_tab = shape == 0 ? c->n_table : c->n_items;
-        if (n_tab) {
-            unsigned grid;
-            const BlockMap bm = block_map(2, n_tab, grid);
-            EvalBitsArgs ba{c->cols, c->excl, nw, c->p0, c->k, c->v, c->items, c->cand_symT, c->cand_out, (uint32_t)c->sF, (uint32_t)c->sR,
-                            (unsigned long long *)device_out, bm, c->cand_diff, shape == 0 ? c->table_ids : (const int32_t *)nullptr,
-                            patch_args(c, 2, n_tab, 64), nullptr, nullptr, c->n_rows, take_clear(), n_clear};
-            hipLaunchKernelGGL(tfn[c->v][shape == 1 ? 1 : 0], dim3(grid + (unsigned)ba.patch.n_blocks), dim3(kBlock), 0, c->stream, ba);
-        }
-    } else if (c->wide) {
-        const EvalArgsT<uint64_t> ea{msa_args(c), c->p0, c->n_pad, c->k, c->items, reinterpret_cast<const CandN<uint64_t> *>(c->cand_n), c->cand_out,
-                                     c->n_extra ? c->extra_off : (const int32_t *)nullptr, reinterpret_cast<const uint64_t *>(c->extra_words), c->sF, c->sR,
-                                     c->v, kmask_of<uint64_t>(c->k), rows, (unsigned long long *)device_out};
-        const dim3 grid((unsigned)c->n_items, (unsigned)split);
-        if (vmode == 0) hipLaunchKernelGGL((eval_kernel<kEvalCC, 0, 1, true, 2, uint64_t>), grid, dim3(kBlock), 0, c->stream, ea);
-        else if (vmode == 1 && !getenv("MP_EVAL_GENERIC_V")) hipLaunchKernelGGL((eval_kernel<kEvalCC, 1, 1, true, 2, uint64_t>), grid, dim3(kBlock), 0, c->stream, ea);
-        else hipLaunchKernelGGL((eval_kernel<kEvalCC, 2, 1, true, 2, uint64_t>), grid, dim3(kBlock), 0, c->stream, ea);
-    } else {
-    EvalArgs ea{msa_args(c), c->p0, c->n_pad, c->k, c->items, reinterpret_cast<const CandN<uint32_t> *>(c->cand_n), c->cand_out,
-                c->n_extra ? c->extra_off : (const int32_t *)nullptr, c->extra_words, (uint32_t)c->sF, (uint32_t)c->sR, c->v, (1u << c->k) - 1u, rows,
-                (unsigned long long *)device_out};
-    int variant = c->eval_variant;
-    if (const char *e = getenv("MP_EVAL_VARIANT")) variant = atoi(e);
-    if (variant < 0 || variant >= kNumEvalVariants) variant = 0;
-    hipLaunchKernelGGL(kEvalVariants[variant].fn[getenv("MP_EVAL_GENERIC_V") ? 2 : vmode], dim3((unsigned)c->n_items, (unsigned)split),
-                       dim3(kBlock), 0, c->stream, ea);
+    int rc = MP_OK;
+    switch (c->form.path) {
+    case EvalForm::BitsX: rc = launch_eval_x(c, out); break;
+    case EvalForm::Bits: rc = launch_bits(c, out, pending_clear, (uint32_t)n_counters); break;
+    case EvalForm::RowsWide: launch_rows(c, out, kEvalWide[c->form.row_vmode]); break;
+    case EvalForm::RowsNarrow: launch_rows(c, out, kEvalVariants[c->form.row_variant].fn[c->form.row_vmode]); break;
+    case EvalForm::None: return fail(c, MP_ERR_ARG, "no candidate set staged");
     }
+    if (rc) return rc;
     if (pending_clear) zero(device_clear);                  // no kernel of this step could take the side job (row-per-lane / program-driven forms)
-    if (timed) {
-        HIPCK(c, hipEventRecord(ev.second, c->stream));
-        c->ev_busy.push_back(ev);
-    }
+    if (timed) { HIPCK(c, hipEventRecord(ev.second, c->stream)); c->ev_busy.push_back(ev); }
     HIPCK(c, hipGetLastError());
     return MP_OK;
 }
@@ -1672,124 +1434,6 @@ int mp_eval_timing_samples(mp_ctx *c, int32_t cap, float *ms, int32_t *n) {
     return MP_OK;
 }
 
-// the statistics launch on the context's current stream into stats_buf (n_f frequency + n_t pair counters)
-static int window_stats_launch(mp_ctx *c, size_t &n_f, size_t &n_t) {
-    const size_t W = (size_t)c->n_win, k = (size_t)c->k;
-    n_f = W * 4 * k; n_t = W * (k - 1) * 16;
-    int rc;
-    if (c->stats_buf_n < n_f + n_t) {
-        dev_free(c, &c->stats_buf, c->stats_buf_n);
-        c->stats_buf_n = 0;
-        if ((rc = dev_alloc(c, &c->stats_buf, n_f + n_t))) return rc;
-        c->stats_buf_n = n_f + n_t;
-    }
-    unsigned long long *d = c->stats_buf;
-    HIPCK(c, hipMemsetAsync(d, 0, sizeof(unsigned long long) * (n_f + n_t), c->stream));
-    const int nw = c->n_pad / 64;
-    // words per thread: 4 from 32768 rows up (8: 0.64 ms against 0.34 at 131072 x 1000 — half the waves, 2: 0.36)
-    const int GW = 2 * nw >= 4 * kBlock ? 4 : (2 * nw >= 2 * kBlock ? 2 : 1);
-    BlockMap m;
-    m.ny = std::max(1, (2 * nw / GW + kBlock - 1) / kBlock);
-    m.ny_pad = m.ny > 4 ? (m.ny + 7) / 8 * 8 : (m.ny > 2 ? 4 : m.ny);
-    m.n_items = c->n_win;
-    const int bands = m.ny_pad >= 8 ? 1 : 8 / m.ny_pad;
-    m.per_band = (c->n_win + bands - 1) / bands;
-    const unsigned grid = m.ny_pad >= 8 ? (unsigned)((size_t)c->n_win * m.ny_pad) : (unsigned)(8 * (size_t)m.per_band);
-    StatsArgs sa{c->cols, c->excl, nw, c->p0, c->k, c->v, m, c->n_win, d, d + n_f, patch_args(c, GW, c->n_win, kBlock)};
-    // [r6] the plain rows of G consecutive windows per workgroup (window_stats_group_kernel) where the alignment is deep enough for the
-    // per-window form to be bound by its L2 re-reads; the patch planes stay with the per-window kernel (its patch blocks only then).
-    // MP_STATS_GROUP=0 keeps the per-window kernel for everything, =4 / 8 picks G.
-    int G = GW == 4 ? 4 : 0;
-    if (const char *e = getenv("MP_STATS_GROUP")) { const int g = atoi(e); G = (g == 4 || g == 8) && GW == 4 ? g : 0; }
-    if (G) {
-        const int n_groups = (c->n_win + G - 1) / G;
-        unsigned ggrid;
-        StatsArgs sg = sa;
-        sg.map = make_block_map(nw, GW, n_groups, ggrid);
-        const dim3 gfull(ggrid + (unsigned)sg.patch.n_blocks);          // (the patch blocks first, as in the per-window launch)
-        if (G == 8) hipLaunchKernelGGL((window_stats_group_kernel<4, 8>), gfull, dim3(kBlock), 0, c->stream, sg);
-        else hipLaunchKernelGGL((window_stats_group_kernel<4, 4>), gfull, dim3(kBlock), 0, c->stream, sg);
-        HIPCK(c, hipGetLastError());
-        return MP_OK;
-    }
-    const dim3 full(grid + (unsigned)sa.patch.n_blocks);
-    if (GW == 4) hipLaunchKernelGGL(window_stats_kernel<4>, full, dim3(kBlock), 0, c->stream, sa);
-    else if (GW == 2) hipLaunchKernelGGL(window_stats_kernel<2>, full, dim3(kBlock), 0, c->stream, sa);
-    else hipLaunchKernelGGL(window_stats_kernel<1>, full, dim3(kBlock), 0, c->stream, sa);
-    HIPCK(c, hipGetLastError());
-    return MP_OK;
-}
-
-int mp_window_stats(mp_ctx *c, int64_t *freq, int64_t *nn) {
-    if (!c) return MP_ERR_ARG;
-    if (!c->excl) return fail(c, MP_ERR_ARG, "no windows built");
-    if (!freq || !nn) return fail(c, MP_ERR_ARG, "null output");
-    HIPCK(c, hipSetDevice(c->dev));
-    int rc;
-    if ((rc = ensure_patch_planes(c))) return rc;
-    size_t n_f = 0, n_t = 0;
-    if ((rc = window_stats_launch(c, n_f, n_t))) return rc;
-    unsigned long long *d = c->stats_buf;
-    HIPCK(c, hipMemcpyAsync(freq, d, sizeof(int64_t) * n_f, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipMemcpyAsync(nn, d + n_f, sizeof(int64_t) * n_t, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return MP_OK;
-}
-
-// [r6] The same in two halves, for a caller that has something else to put on the device's copy engines meanwhile — the streamed planning
-// (mp_plan_create_streamed) reads 50-100 MB of histogram entries back while the statistics kernel (2.8 ms at 10^6 rows) runs: begin
-// launches the kernel and the read-back of its counters into a registered buffer of the context on the SECOND stream and returns at once;
-// end waits for them and hands the counters over.  mp_plan_create_streamed calls end itself (before its planners read a counter) when a
-// begin is pending and is given the arrays the counters belong in.
-int mp_window_stats_begin(mp_ctx *c) {
-    if (!c) return MP_ERR_ARG;
-    if (!c->excl) return fail(c, MP_ERR_ARG, "no windows built");
-    HIPCK(c, hipSetDevice(c->dev));
-    int rc;
-    if ((rc = ensure_patch_planes(c))) return rc;                      // (on the first stream)
-    if (!c->alt_stream) HIPCK(c, hipStreamCreateWithFlags(&c->alt_stream, hipStreamNonBlocking));
-    if (!c->stats_ev) HIPCK(c, hipEventCreateWithFlags(&c->stats_ev, hipEventDisableTiming));
-    // the second stream starts behind everything the first has queued so far (planes, windows, patch planes)
-    HIPCK(c, hipEventRecord(c->stats_ev, c->stream));
-    HIPCK(c, hipStreamWaitEvent(c->alt_stream, c->stats_ev, 0));
-    const size_t W = (size_t)c->n_win, k = (size_t)c->k, n = W * 4 * k + W * (k - 1) * 16, bytes = sizeof(int64_t) * n;
-    if (c->h_stats_bytes < bytes) {
-        if (c->h_stats) { if (c->h_stats_pinned) (void)hipHostUnregister(c->h_stats); host_unmap(c->h_stats, c->h_stats_bytes); }
-        c->h_stats_pinned = false; c->h_stats_bytes = 0;
-        const size_t room = (bytes + ((size_t)2 << 20) - 1) / ((size_t)2 << 20) * ((size_t)2 << 20);
-        c->h_stats = static_cast<uint8_t *>(host_map(room));
-        if (!c->h_stats) return fail(c, MP_ERR_NOMEM, "mp_window_stats_begin: out of host memory");
-        c->h_stats_bytes = room;
-        prefault_host(c->h_stats, room);
-        if (!getenv("MP_NO_PIN") && hipHostRegister(c->h_stats, room, hipHostRegisterDefault) == hipSuccess) c->h_stats_pinned = true;
-        else (void)hipGetLastError();
-    }
-    hipStream_t keep = c->stream;
-    c->stream = c->alt_stream;
-    size_t n_f = 0, n_t = 0;
-    rc = window_stats_launch(c, n_f, n_t);
-    hipError_t e = hipSuccess;
-    if (rc == MP_OK) e = hipMemcpyAsync(c->h_stats, c->stats_buf, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (rc == MP_OK && e == hipSuccess) e = hipEventRecord(c->stats_ev, c->stream);
-    c->stream = keep;
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "mp_window_stats_begin: %s", hipGetErrorString(e));
-    c->stats_pending_f = n_f; c->stats_pending_t = n_t;
-    return MP_OK;
-}
-
-int mp_window_stats_end(mp_ctx *c, int64_t *freq, int64_t *nn) {
-    if (!c) return MP_ERR_ARG;
-    if (!c->stats_pending_f) return fail(c, MP_ERR_ARG, "mp_window_stats_end: no mp_window_stats_begin is pending");
-    if (!freq || !nn) return fail(c, MP_ERR_ARG, "null output");
-    HIPCK(c, hipSetDevice(c->dev));
-    HIPCK(c, hipEventSynchronize(c->stats_ev));
-    memcpy(freq, c->h_stats, sizeof(int64_t) * c->stats_pending_f);
-    memcpy(nn, c->h_stats + sizeof(int64_t) * c->stats_pending_f, sizeof(int64_t) * c->stats_pending_t);
-    c->stats_pending_f = c->stats_pending_t = 0;
-    return MP_OK;
-}
-
 int mp_eval_candidates(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *codes, uint64_t sF, uint64_t sR,
                        int64_t *out) {
     if (!c) return MP_ERR_ARG;
@@ -1808,7 +1452,6 @@ int mp_eval_candidates(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8
     HIPCK(c, hipStreamSynchronize(c->stream));
     return MP_OK;
 }
-
 
 int mp_eval_masks_resident(mp_ctx *c, int32_t n_cand, const int32_t *cw, const uint8_t *codes, uint64_t sF, uint64_t sR) {
     if (!c) return MP_ERR_ARG;

@@ -1,4 +1,5 @@
-// evalprog.hpp — fetch programs of the chain items (evalprog.hip): layout constants and entry points.
+// evalprog.hpp — fetch programs of the chain items (evalprog.hip): layout constants and entry points.  Whether the programs are written,
+// and for which shape, is decided at upload (choose_eval_form in eval.hip; mp_ctx::form.use_prog / chain_shape).
 //
 // One block of kProgRegs x 64 32-bit entries per chain item, register q = entries [64 q, 64 q + 64), one entry per lane:
 //   register 0: lanes 0-23 the output slot (candidate index or -1) of counter lane / 3 — where the commit's lanes look for it;

@@ -151,6 +151,27 @@ def test_product_never_reaches_into_the_oracle():
             assert "oracle/" not in open(path).read().replace("oracle/core_ref.py", ""), path
 
 
+def test_eval_form_switches_are_read_in_one_place():
+    """The switches that pick the evaluation's kernel form are read once, when a candidate set is staged (choose_eval_form in eval.hip):
+    each appears in exactly one getenv of the library, all in that function, and the launch path below it reads the timing switch only."""
+    csrc = os.path.join(REPO, "multiprime_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".cpp", ".hpp"))}
+    ev = text["eval.hip"]
+    chooser = ev[ev.index("static void choose_eval_form("):ev.index("static int launch_chains(")]
+    for name in ("MP_EVAL_MODE", "MP_EVAL_BITS", "MP_EVAL_CHAIN", "MP_EVAL_PROG", "MP_EVAL_X_SHAPE", "MP_EVAL_GENERIC_V", "MP_EVAL_VARIANT"):
+        call = 'getenv("%s")' % name
+        assert sum(t.count(call) for t in text.values()) == 1, name
+        assert call in chooser, name
+    for a, b in (("static int launch_eval_x(", "static void choose_eval_form("), ("static int launch_chains(", 'extern "C" {'),
+                 ("static int eval_launch_impl(", "int mp_eval_launch(")):
+        launch = ev[ev.index(a):]
+        assert re.findall(r'getenv\("(\w+)"\)', launch[:launch.index(b)]) == (["MP_EVAL_TIMING_EVERY"] if "impl" in a else []), a
+    for f in ("evalprog.hip", "evalslide.hip"):                    # launch_eval_prog / launch_eval_slide: the stamps experiment only
+        assert set(re.findall(r'getenv\("(MP_EVAL_\w+)"\)', text[f])) <= {"MP_EVAL_SLIDE"}, f
+    import __graft_entry__ as g
+    assert sorted(f for f in text if f.endswith((".hip", ".cpp"))) == sorted(g.HIP_SOURCES)
+
+
 def test_implicit_loader_refuses_a_backend_that_is_not_hip(oracle_lib, monkeypatch):
     """Library() without a path is the product's loader: no environment variable can put the CPU checker behind a drop-in command.
     Library(path) — tests, tools — loads what it is told to; the CLI tests patch the class from tests/checker_shim/."""

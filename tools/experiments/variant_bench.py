@@ -70,16 +70,15 @@ def main():
                 os.environ["MP_EVAL_TILE_GROUPS"] = var.split(":")[1]
             else:
                 os.environ.pop("MP_EVAL_TILE_GROUPS", None)
-            ctx.eval_upload(cw, codes, sF, sR)           # a new plan
         elif var[0] in "cpq":  # cN: eval_chain_kernel shape N; pN: the program-driven kernel, same shapes (+ 9); qN: the same with a wave per item
             os.environ["MP_EVAL_BITS"] = "0"
             os.environ["MP_EVAL_TILE"] = "0"
             os.environ["MP_EVAL_PROG"] = "1" if var[0] in "pq" else "0"
             os.environ["MP_EVAL_QUAD"] = "1" if var[0] == "q" else "0"
             os.environ["MP_EVAL_CHAIN"] = var[1:]
-            ctx.eval_upload(cw, codes, sF, sR)           # the programs are written at upload time
         else:
             os.environ["MP_EVAL_BITS"] = var[1:]
+        ctx.eval_upload(cw, codes, sF, sR)               # the form switches are read when a candidate set is staged
         for _ in range(3):
             ctx.eval_launch(out.data_ptr())
         ctx.eval_timing(reset=True)
