@@ -45,7 +45,34 @@ int mp_offtarget_resident(struct mp_ctx *ctx, int32_t n_patterns, const uint8_t 
 int mp_amplicon_join(struct mp_ctx *ctx, int64_t n_sites, const int32_t *sites, int32_t size_lo, int32_t size_hi, int64_t cap,
                      int32_t *out, int64_t *n_out);
 
-/* Of the last mp_offtarget_resident / mp_amplicon_join of this context: ms[4] = {scan, site reduction, join, whole call} (device
+/* ---- the gapped rule: bowtie2's end-to-end scoring with at most one short gap ------------------------------------------------------
+ * A read of L bases as the text reads it (the read, or its reverse complement on strand 1) hits row T at the 0-based start p when the
+ * ungapped rule of mp_kmm_scan holds with max_penalty / 6 mismatches, or when one of these alignments exists for a gap of
+ * g = 1 .. max_gap bases and a split c:
+ *   type D (c M, g D, (L - c) M)          read base j pairs with T[p + j] for j < c and with T[p + g + j] for j >= c;
+ *                                         MP_KMM_GBAR <= c <= L - MP_KMM_GBAR, p + L + g <= len(T); the skipped text bases may be anything
+ *   type I (c M, g I, (L - c - g) M)      read base j pairs with T[p + j] for j < c and with T[p + j - g] for j >= c + g;
+ *                                         MP_KMM_GBAR <= c, c + g <= L - MP_KMM_GBAR, p + L - g <= len(T)
+ * with 6 * mismatches + 5 + 3 * g <= max_penalty (a pair mismatches as in mp_kmm_scan: different bases, or a text base outside
+ * A/C/G/T) and a trailing run of at least `term` matching pairs, counted from the read's last base (as the text reads it) downwards
+ * over aligned pairs: it ends at the first mismatch, ends at a deletion, and passes over inserted bases (an MD:Z tag does not show
+ * them).  A site is reported once however many alignments reach it.  max_gap = 0 is the ungapped rule exactly.  Not covered: two
+ * gaps in one alignment (bowtie2's default scoring admits them from L = 26 on) and gaps longer than MP_KMM_MAX_GAP. */
+#define MP_KMM_GBAR 4
+#define MP_KMM_MAX_GAP 4
+
+/* mp_kmm_scan_resident (mprime.h) under the gapped rule: hits {sequence, start, pattern, strand} of the store of mp_seq_load, cap /
+ * *n_hits as there.  MP_ERR_ARG when max_gap is outside 0 .. MP_KMM_MAX_GAP or max_penalty < 0. */
+int mp_kmm_gap_scan_resident(struct mp_ctx *ctx, int32_t n_patterns, const uint8_t *pat_codes, const int32_t *pat_off, int32_t max_penalty,
+                             int32_t max_gap, int32_t term, int64_t cap, int32_t *hits, int64_t *n_hits);
+
+/* mp_offtarget_resident under the gapped rule: max_penalty[i] is read i's penalty ceiling (one launch per distinct ceiling); the site
+ * reduction, the join, the kept products and mp_offtarget_stats are those of mp_offtarget_resident. */
+int mp_offtarget_gap_resident(struct mp_ctx *ctx, int32_t n_patterns, const uint8_t *pat_codes, const int32_t *pat_off,
+                              const int32_t *read_primer, const int32_t *max_penalty, int32_t max_gap, int32_t term, int32_t size_lo,
+                              int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out);
+
+/* Of the last mp_offtarget_resident / mp_offtarget_gap_resident / mp_amplicon_join of this context: ms[4] = {scan, site reduction, join, whole call} (device
  * event times of the first three stages; the whole call on the host clock, copies included) and counts[7] = {hits, forward sites,
  * reverse sites, products, sequences with forward sites, with reverse sites, with both}.  A call served from the kept products
  * reports zero device times and the counts of the call that made them. */

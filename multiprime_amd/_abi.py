@@ -97,6 +97,14 @@ OFFTARGET_SYMBOLS = [
     ("mp_amplicon_join", C.c_int, [_p, C.c_int64, _p, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
     ("mp_offtarget_stats", C.c_int, [_p, _p, _p]),
 ]
+# the gapped rule of the same header (csrc/kmm.hpp: kmm_gap_kernel): bound the same way; a library without them (the oracle) leaves
+# validate.py to its host form of the rule
+GAP_SYMBOLS = [
+    ("mp_kmm_gap_scan_resident", C.c_int, [_p, C.c_int32, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
+    ("mp_offtarget_gap_resident", C.c_int, [_p, C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _p,
+                                            C.POINTER(C.c_int64)]),
+]
+KMM_MAX_GAP = 4                     # MP_KMM_MAX_GAP
 
 
 def prefer_staged_copies():
@@ -187,7 +195,10 @@ class Library:
         self.offtarget = all(hasattr(self.dll, name) for name, _, _ in OFFTARGET_SYMBOLS)
         if self.backend == "hip" and not self.offtarget:
             raise MprimeError(-2, f"{path} lacks the off-target entry points of include/mprime_offtarget.h: rebuild it")
-        for name, res, args in OFFTARGET_SYMBOLS if self.offtarget else ():
+        self.gapscan = all(hasattr(self.dll, name) for name, _, _ in GAP_SYMBOLS)
+        if self.backend == "hip" and not self.gapscan:
+            raise MprimeError(-2, f"{path} lacks the gapped-scan entry points of include/mprime_offtarget.h: rebuild it")
+        for name, res, args in (OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -641,6 +652,23 @@ class Context:
                 return h[np.lexsort((h[:, 3], h[:, 2], h[:, 1], h[:, 0]))] if len(h) else h
             cap = int(n.value)
 
+    def kmm_gap_scan_resident(self, pat_codes, pat_off, max_penalty: int, max_gap: int, term: int, cap: int = 1 << 20) -> np.ndarray:
+        """kmm_scan_resident under the gapped rule of include/mprime_offtarget.h: one gap of up to `max_gap` bases beside the mismatches,
+        6 per mismatch and 5 + 3 g per gap within `max_penalty`."""
+        if not self.lib.gapscan:
+            raise MprimeError(-2, f"{self.lib.path} has no gapped scan (libmprime_hip.so does; validate.gap_scan_host is its host form)")
+        pat_codes = np.ascontiguousarray(pat_codes, dtype=np.uint8)
+        pat_off = np.ascontiguousarray(pat_off, dtype=np.int32)
+        while True:
+            hits = np.empty((max(cap, 1), 4), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_kmm_gap_scan_resident(self.h, len(pat_off) - 1, _ptr(pat_codes), _ptr(pat_off), int(max_penalty), int(max_gap),
+                                                     int(term), cap, _ptr(hits), C.byref(n)))
+            if n.value <= cap:
+                h = hits[: n.value]
+                return h[np.lexsort((h[:, 3], h[:, 2], h[:, 1], h[:, 0]))] if len(h) else h
+            cap = int(n.value)
+
     # include/mprime_offtarget.h
     def _need_offtarget(self):
         if not self.lib.offtarget:
@@ -661,6 +689,24 @@ class Context:
             n = C.c_int64(0)
             self._ck(self.d.mp_offtarget_resident(self.h, n_pat, _ptr(pat_codes), _ptr(pat_off), _ptr(read_primer), _ptr(mm), int(term),
                                                   int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
+            if n.value <= cap:
+                return out[: n.value]
+            cap = int(n.value)
+
+    def offtarget_gap_resident(self, pat_codes, pat_off, read_primer, max_penalty, max_gap: int, term: int, size_lo: int, size_hi: int,
+                               cap: int = 1 << 20) -> np.ndarray:
+        """offtarget_resident under the gapped rule: max_penalty per read (or one for all), one gap of up to `max_gap` bases."""
+        self._need_offtarget()
+        pat_codes = np.ascontiguousarray(pat_codes, dtype=np.uint8)
+        pat_off = np.ascontiguousarray(pat_off, dtype=np.int32)
+        n_pat = len(pat_off) - 1
+        read_primer = np.ascontiguousarray(read_primer, dtype=np.int32)
+        pen = np.ascontiguousarray(np.broadcast_to(np.asarray(max_penalty, np.int32), (n_pat,)), dtype=np.int32)
+        while True:
+            out = np.empty((max(cap, 1), 6), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_offtarget_gap_resident(self.h, n_pat, _ptr(pat_codes), _ptr(pat_off), _ptr(read_primer), _ptr(pen), int(max_gap),
+                                                      int(term), int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
             if n.value <= cap:
                 return out[: n.value]
             cap = int(n.value)

@@ -354,15 +354,15 @@ double ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
-}  // namespace
-
-extern "C" {
-
-int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
-                          const int32_t *max_mm, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {
+// The screen behind both entry points.  max_gap < 0: mp_offtarget_resident — max_mm[i] is read i's mismatch budget (kmm_kernel);
+// max_gap >= 0: mp_offtarget_gap_resident — max_mm[i] is read i's penalty ceiling, and a table whose ceiling admits a gap goes through
+// kmm_gap_kernel (the others through kmm_kernel with ceiling / 6 mismatches: the same sites).
+int offtarget_run(mp_ctx *c, const char *who, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
+                  const int32_t *max_mm, int32_t max_gap, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {
     if (!c) return MP_ERR_ARG;
     if (n_pat < 0 || !n_out || cap < 0 || (cap && !out) || (n_pat && (!pat_codes || !pat_off || !read_primer || !max_mm)) || term < 0)
-        return fail(c, MP_ERR_ARG, "mp_offtarget_resident: bad arguments");
+        return fail(c, MP_ERR_ARG, "%s: bad arguments", who);
+    if (max_gap > MP_KMM_MAX_GAP) return fail(c, MP_ERR_ARG, "%s: max_gap %d (0..%d)", who, max_gap, MP_KMM_MAX_GAP);
     HIPCK(c, hipSetDevice(c->dev));
     const auto t0 = std::chrono::steady_clock::now();
     *n_out = 0;
@@ -374,7 +374,7 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
             const uint8_t m = pat_codes[pat_off[i] + j];
             if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
         }
-        if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative mismatch budget", i);
+        if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative %s", i, max_gap < 0 ? "mismatch budget" : "penalty ceiling");
     }
     if (c->sq_n == 0 || n_pat == 0) {
         for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
@@ -385,8 +385,8 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
     }
     // a repeat of the last call (a larger cap after *n_out > cap): its products are still on the device
     std::vector<uint8_t> key;
-    const int32_t head[4] = {n_pat, term, size_lo, size_hi};
-    put(key, head, 4);
+    const int32_t head[5] = {n_pat, term, size_lo, size_hi, max_gap};
+    put(key, head, 5);
     put(key, pat_off, (size_t)n_pat + 1);
     put(key, pat_codes + pat_off[0], (size_t)(pat_off[n_pat] - pat_off[0]));
     put(key, read_primer, (size_t)n_pat);
@@ -407,11 +407,11 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
         for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
     }
     const size_t nb = std::max<size_t>(blk_row.size(), 1);
-    // one pattern table per mismatch budget (ids: the global read index)
+    // one pattern table per mismatch budget / penalty ceiling (ids: the global read index)
     std::vector<int32_t> budgets(max_mm, max_mm + n_pat);
     std::sort(budgets.begin(), budgets.end());
     budgets.erase(std::unique(budgets.begin(), budgets.end()), budgets.end());
-    struct Table { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; };
+    struct Table { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; int32_t gaps; };
     std::vector<Table> tables;
     for (int32_t b : budgets) {
         std::vector<uint8_t> codes;
@@ -424,7 +424,9 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
             ids.push_back(i);
             longest = std::max(longest, pat_off[i + 1] - pat_off[i]);
         }
-        Table T{b, longest > 32, {}, 0};
+        // gap lengths this ceiling admits (5 + 3 g <= ceiling); none: kmm_kernel with ceiling / 6 mismatches
+        Table T{b, longest > 32, {}, 0, max_gap > 0 && b >= 8 ? std::min<int32_t>(max_gap, (b - 5) / 3) : 0};
+        if (max_gap >= 0 && T.gaps == 0) T.budget = b / 6;
         auto fill = [&](auto &pats) {
             kmm_patterns(off.size() - 1, codes.data(), off.data(), term, pats);
             for (auto &P : pats) P.id = ids[(size_t)P.id];
@@ -468,7 +470,7 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
         if (e == hipSuccess) e = hipMemcpyAsync(d_bseg, blk_seg.data(), sizeof(int32_t) * blk_seg.size(), hipMemcpyHostToDevice, c->stream);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(d_rp, read_primer, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "mp_offtarget_resident: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
     FillSeg seg{row_min, sizeof(int32_t) * (size_t)n_rows, 0x7fffffffu};
     if ((rc = fill_segments(c, &seg, 1))) { destroy_events(); cleanup(); return rc; }
     OtSites sink{map, c->sq_roff, n_bases, row_min, d_hits};
@@ -476,7 +478,17 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
         if (blk_row.empty()) break;
         e = hipMemcpyAsync(d_pats, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) break;
-        if (T.two)
+        if (T.gaps > 0 && T.two)
+            hipLaunchKernelGGL((kmm_gap_kernel<2, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const int64_t *)c->sq_roff,
+                               (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag, (const int64_t *)c->sq_woff,
+                               (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats), T.n, (int)T.budget,
+                               (int)T.gaps, (int)term, sink);
+        else if (T.gaps > 0)
+            hipLaunchKernelGGL((kmm_gap_kernel<1, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const int64_t *)c->sq_roff,
+                               (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag, (const int64_t *)c->sq_woff,
+                               (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<1> *>(d_pats), T.n, (int)T.budget,
+                               (int)T.gaps, (int)term, sink);
+        else if (T.two)
             hipLaunchKernelGGL((kmm_kernel<2, true, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
                                (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
                                (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats),
@@ -527,6 +539,22 @@ int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, co
     rc = copy_out(c, cap, out, n_out);
     c->ot_ms[3] = ms_since(t0);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
+                          const int32_t *max_mm, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {
+    return offtarget_run(c, "mp_offtarget_resident", n_pat, pat_codes, pat_off, read_primer, max_mm, -1, term, size_lo, size_hi, cap, out, n_out);
+}
+
+int mp_offtarget_gap_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
+                              const int32_t *max_pen, int32_t max_gap, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out,
+                              int64_t *n_out) {
+    if (c && max_gap < 0) return fail(c, MP_ERR_ARG, "mp_offtarget_gap_resident: max_gap %d (0..%d)", max_gap, MP_KMM_MAX_GAP);
+    return offtarget_run(c, "mp_offtarget_gap_resident", n_pat, pat_codes, pat_off, read_primer, max_pen, max_gap, term, size_lo, size_hi, cap, out, n_out);
 }
 
 int mp_amplicon_join(mp_ctx *c, int64_t n_sites, const int32_t *sites, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {

@@ -11,6 +11,7 @@
 // ~10 wave-instructions per (64 positions, pattern).
 #include "common.hpp"
 #include "kmm.hpp"
+#include "../../include/mprime_offtarget.h"
 
 using namespace mp;
 
@@ -45,10 +46,11 @@ __global__ __launch_bounds__(kBlock) void seq_pack_kernel(const uint8_t *__restr
     }
 }
 
-// the scan itself on device text (bytes of this call, or the resident store when `code` is set)
+// the scan itself on device text (bytes of this call, or the resident store when `code` is set); max_gap > 0: the gapped rule of
+// mprime_offtarget.h on the resident store with the penalty ceiling `pen` (kmm_gap_kernel), else max_mm mismatches (kmm_kernel)
 int kmm_scan_device(mp_ctx *c, const uint8_t *d_bytes, const int64_t *d_roff, const unsigned long long *code, const unsigned long long *flag,
                     const int64_t *d_woff, const int64_t *roff_host, int32_t n_rows, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off,
-                    int32_t max_mm, int32_t term, int64_t cap, int32_t *hits, int64_t *n_hits) {
+                    int32_t max_mm, int32_t term, int64_t cap, int32_t *hits, int64_t *n_hits, int32_t pen = 0, int32_t max_gap = 0) {
     int longest = 0;
     for (int32_t i = 0; i < n_pat; i++) {
         const int len = pat_off[i + 1] - pat_off[i];
@@ -94,9 +96,15 @@ int kmm_scan_device(mp_ctx *c, const uint8_t *d_bytes, const int64_t *d_roff, co
 #define MP_KMM_LAUNCH(NW, RES)                                                                                                               \
     hipLaunchKernelGGL((kmm_kernel<NW, RES, KmmAppend>), dim3((unsigned)nb), dim3(kBlock), 0, c->stream, d_bytes, d_roff, code, flag, d_woff, \
                        d_brow, d_bseg, reinterpret_cast<const KmmPat<NW> *>(d_pats), (int)n_entries, (int)max_mm, KmmAppend{(long long)cap, d_hits, d_n})
-        if (code) { if (two_words) MP_KMM_LAUNCH(2, true); else MP_KMM_LAUNCH(1, true); }
+#define MP_KMM_GAP_LAUNCH(NW)                                                                                                                 \
+    hipLaunchKernelGGL((kmm_gap_kernel<NW, KmmAppend>), dim3((unsigned)nb), dim3(kBlock), 0, c->stream, d_roff, code, flag, d_woff, d_brow, d_bseg, \
+                       reinterpret_cast<const KmmPat<NW> *>(d_pats), (int)n_entries, (int)pen, (int)max_gap, (int)term,                         \
+                       KmmAppend{(long long)cap, d_hits, d_n})
+        if (code && max_gap > 0) { if (two_words) MP_KMM_GAP_LAUNCH(2); else MP_KMM_GAP_LAUNCH(1); }
+        else if (code) { if (two_words) MP_KMM_LAUNCH(2, true); else MP_KMM_LAUNCH(1, true); }
         else { if (two_words) MP_KMM_LAUNCH(2, false); else MP_KMM_LAUNCH(1, false); }
 #undef MP_KMM_LAUNCH
+#undef MP_KMM_GAP_LAUNCH
         e = hipGetLastError();
     }
     unsigned long long n = 0;
@@ -216,6 +224,21 @@ int mp_kmm_scan_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, con
     if (c->sq_n == 0 || n_pat == 0) return MP_OK;
     return kmm_scan_device(c, c->sq_bytes, c->sq_roff, c->sq_code, c->sq_flag, c->sq_woff, c->sq_roff_host.data(), c->sq_n, n_pat, pat_codes, pat_off,
                            max_mm, term, cap, hits, n_hits);
+}
+
+int mp_kmm_gap_scan_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, int32_t max_pen, int32_t max_gap,
+                             int32_t term, int64_t cap, int32_t *hits, int64_t *n_hits) {
+    if (!c) return MP_ERR_ARG;
+    if (n_pat < 0 || !n_hits || cap < 0 || (cap && !hits) || (n_pat && (!pat_codes || !pat_off)) || max_pen < 0 || term < 0)
+        return fail(c, MP_ERR_ARG, "mp_kmm_gap_scan_resident: bad arguments");
+    if (max_gap < 0 || max_gap > MP_KMM_MAX_GAP) return fail(c, MP_ERR_ARG, "mp_kmm_gap_scan_resident: max_gap %d (0..%d)", max_gap, MP_KMM_MAX_GAP);
+    HIPCK(c, hipSetDevice(c->dev));
+    *n_hits = 0;
+    if (c->sq_n == 0 || n_pat == 0) return MP_OK;
+    // no gap fits under the ceiling (5 + 3 g > max_penalty), or none is asked for: the ungapped kernel, exactly
+    const int32_t gaps = max_pen >= 8 ? std::min<int32_t>(max_gap, (max_pen - 5) / 3) : 0;
+    return kmm_scan_device(c, c->sq_bytes, c->sq_roff, c->sq_code, c->sq_flag, c->sq_woff, c->sq_roff_host.data(), c->sq_n, n_pat, pat_codes, pat_off,
+                           max_pen / 6, term, cap, hits, n_hits, max_pen, gaps);
 }
 
 }  // extern "C"

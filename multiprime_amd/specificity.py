@@ -15,7 +15,8 @@ only in its defaults and reports:
 What differs from V9, pinned by tests/golden/specificity.json.gz (make_golden_specificity.py, the unmodified reference class on SAM
 input): the defaults (-l 18, -t 4, -s 100,1500, -m 1; the class's own: term_length 9, size "150,2000"), the optparse command line,
 <out>.total.acc.num without a trailing newline, and no target dictionary (-d) and so no .unmatched.fa.  Sequences come out in the
-order of their first forward hit (smallest read, then sequence), where the reference walks a Python set.
+order of their first forward hit (smallest read, then sequence), where the reference walks a Python set.  `--gaps` (gaps=True)
+switches the mapper rule to validate.py's gapped one (mp_offtarget_gap_resident: the same reduction and join behind kmm_gap_kernel).
 """
 from __future__ import annotations
 
@@ -27,14 +28,14 @@ from pathlib import Path
 import numpy as np
 
 from . import iupac
-from ._abi import Library
-from .validate import _READ_INDEX, TermTable, amplicons, bowtie2_mismatch_budget, sites_of_sam, usable_reads
+from ._abi import KMM_MAX_GAP, Library
+from .validate import _READ_INDEX, TermTable, amplicons, bowtie2_mismatch_budget, bowtie2_penalty_ceiling, sites_of_sam, usable_reads
 
 
 class off_targets(object):
     def __init__(self, primer_file, term_length=9, reference_file="", mismatch_num=1, term_threshold=4, bowtie="",
                  PCR_product_size="150,2000", outfile="", nproc=10, *, library: Library | None = None, device: int = 0,
-                 max_mismatch=None, join="device"):
+                 max_mismatch=None, join="device", gaps=False):
         self.bowtie = bowtie                    # accepted for compatibility: no external mapper is run
         self.term_threshold = int(term_threshold)
         self.nproc = nproc
@@ -45,6 +46,7 @@ class off_targets(object):
         self.PCR_size = PCR_product_size
         self.mismatch_num = mismatch_num        # bowtie's -N / -n: seed sensitivity only, the scan is exhaustive
         self.max_mismatch = max_mismatch
+        self.gaps = bool(gaps)                  # validate.py's gapped rule (mp_offtarget_gap_resident); off: the ungapped rule
         if join not in ("device", "host"):
             raise ValueError("join is 'device' (the product) or 'host' (validate.py's scan, sites and amplicons(): the check)")
         self.join = join
@@ -100,8 +102,13 @@ class off_targets(object):
             t1 = time.time()
             ctx.seq_load(data, row_off)
             t2 = time.time()
-            prod = ctx.offtarget_resident(codes, off, np.array([ids[p] for p in primer_of], np.int32), np.array(budget, np.int32),
-                                          self.term_threshold, lo, hi)
+            if self.gaps:
+                pen = [6 * self.max_mismatch if self.max_mismatch is not None else bowtie2_penalty_ceiling(len(seqs[i])) for i in usable]
+                prod = ctx.offtarget_gap_resident(codes, off, np.array([ids[p] for p in primer_of], np.int32), np.array(pen, np.int32),
+                                                  KMM_MAX_GAP, self.term_threshold, lo, hi)
+            else:
+                prod = ctx.offtarget_resident(codes, off, np.array([ids[p] for p in primer_of], np.int32), np.array(budget, np.int32),
+                                              self.term_threshold, lo, hi)
             t3 = time.time()
             ms, counts = ctx.offtarget_stats()
         finally:
@@ -116,7 +123,7 @@ class off_targets(object):
         t0 = time.time()
         forward, reverse = validate.off_targets(self.primer_file, self.term_len, self.reference_file, self.PCR_size, self.mismatch_num,
                                                 self.outfile, self.term_threshold, library=self._library, device=self._device,
-                                                max_mismatch=self.max_mismatch).scan(table)
+                                                max_mismatch=self.max_mismatch, gaps=self.gaps).scan(table)
         t1 = time.time()
         out = self.products_of_sites(forward, reverse)
         self.stats.update(host_sites_s=t1 - t0, host_join_s=time.time() - t1)
@@ -158,7 +165,7 @@ class off_targets(object):
 
 
 def make_parser():
-    """The reference's optparse command line (same options, defaults and destinations), plus --max-mismatch and --device."""
+    """The reference's optparse command line (same options, defaults and destinations), plus --max-mismatch, --gaps and --device."""
     from optparse import OptionParser
     parser = OptionParser('Usage: %prog -i [input] -r [reference fasta] -l [150,2000] -p [10]-o [output]', version="%prog 0.0.6")
     parser.add_option('-i', '--input', dest='input_file', help='input file: primer.fa.')
@@ -175,6 +182,9 @@ def make_parser():
     parser.add_option('-o', '--out', dest='out', help='Prodcut of PCR product with primers.')
     parser.add_option('--max-mismatch', dest='max_mismatch', default=None, type="int",
                       help="mismatches per alignment (default: bowtie2's budget floor((0.6 + 0.6 L) / 6))")
+    parser.add_option('--gaps', dest='gaps', default=False, action="store_true",
+                      help="also admit bowtie2's one short gap (5 + 3 g for g <= 4 bases, at least 4 bases from the read ends) within the "
+                           "same minimum score; default: ungapped")
     parser.add_option('--device', dest='device', default=0, type="int")
     return parser
 
@@ -203,6 +213,6 @@ def main(argv=None):
     options, _ = parse_args(argv)
     off_targets(primer_file=options.input_file, term_length=options.len, reference_file=options.ref, PCR_product_size=options.size,
                 mismatch_num=options.seedmms, outfile=options.out, term_threshold=options.term, bowtie=options.bowtie, nproc=options.proc,
-                device=options.device, max_mismatch=options.max_mismatch).run()
+                device=options.device, max_mismatch=options.max_mismatch, gaps=options.gaps).run()
     e2 = time.time()
     print("INFO {} Total times: {}".format(time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(time.time())), round(float(e2 - e1), 2)))

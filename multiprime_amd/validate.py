@@ -20,8 +20,16 @@ under default end-to-end scoring — an ungapped alignment with at most floor((0
 reference author's own bowtie2 + samtools run of rule BWT_validation (multiPrime.py:441-457), whose output ships in the reference
 tree: all 1158 sequences whose text is available (485 with a product row, 673 without) are decided identically, and the
 neighbouring rules (budget 0 / 2, 3'-term threshold 0 / 2) are not (tests/golden/make_golden_bwt.py, tests/test_validate_bwt.py).
-Beyond what that run exercises: no gapped alignments here (bowtie2 admits a single 1-base gap at L >= 13: score -8 against a
-minimum of -0.6 - 0.6 L); sites bowtie2's seed heuristics (-N, -L 8) miss are found here.
+Beyond what that run exercises: sites bowtie2's seed heuristics (-N, -L 8) miss are found here, and GAPS are opt-in (`gaps=True`,
+`--gaps`).  bowtie2's default scoring charges 5 + 3 g for a gap of g bases on either side and keeps gaps `--gbar 4` bases away from
+the read ends, so under the same minimum score an 18-base term may carry a 1- or 2-base indel instead of its mismatch, a 23-base
+term a 1-base indel and a mismatch.  With `gaps` a site counts when the ungapped rule holds, or when ONE gap of g <= 4 bases, at
+least 4 bases from either end of the read, leaves 6 mm + 5 + 3 g within the penalty ceiling floor(0.6 + 0.6 L) (6 M under
+`--max-mismatch M`) and the last `-t` aligned pairs match — the MD:Z reading of sites_of_sam: the run ends at a deletion and passes
+over inserted bases (include/mprime_offtarget.h states the rule; csrc/kmm.hpp: kmm_gap_kernel; gap_scan_host below is its host
+form).  What remains different with `gaps`: two gaps in one alignment (they fit from L = 26 on) and gaps longer than 4 bases
+(from L = 29 on) are not looked for.  Without `gaps` every output is what it was: the recorded run does not tell the two rules
+apart (tests/test_gapscan.py), so the default stays ungapped.
 
 Orders the reference takes from a Python set (sequences in <out>, names inside a shared term id, unmatched records) are
 deterministic here: first appearance in the forward sites / the primer file / sorted names.
@@ -38,7 +46,7 @@ from pathlib import Path
 import numpy as np
 
 from . import iupac
-from ._abi import Library
+from ._abi import KMM_MAX_GAP, Library
 from .dimer import PATTERN_MAX_LEN
 
 _READ_INDEX = re.compile(r"_\d+$")          # a read name ends in the index of its expansion (V9:249)
@@ -57,6 +65,78 @@ def degenerate_seq(primer: str):
 def bowtie2_mismatch_budget(length: int) -> int:
     """Mismatches bowtie2 --end-to-end admits with default scoring: min score -0.6 - 0.6 L, 6 per mismatch (high quality)."""
     return int((0.6 + 0.6 * length) // 6)
+
+
+def bowtie2_penalty_ceiling(length: int) -> int:
+    """floor(0.6 + 0.6 L): what an end-to-end alignment may lose under default scoring (6 per mismatch, 5 + 3 g per gap)."""
+    return int(0.6 + 0.6 * length)          # in floating point, as bowtie2_mismatch_budget: ceiling // 6 is that budget at every length
+
+
+GBAR = 4                                    # bowtie2 --gbar: no gap within 4 bases of either read end
+_BASE_CODE = np.full(256, 4, np.uint8)      # A C G T (either case) -> 0..3, everything else 4: matches nothing
+for _i, _ch in enumerate("ACGT"):
+    _BASE_CODE[ord(_ch)] = _BASE_CODE[ord(_ch.lower())] = _i
+
+
+def gap_scan_host(data, row_off, reads, max_penalty, max_gap, term):
+    """The gapped rule of include/mprime_offtarget.h on the host, vectorised over start positions: hits [n][4] = (sequence, start,
+    read, strand) sorted as Context.kmm_scan sorts them.  `reads`: concrete ACGT strings.  The checker of mp_kmm_gap_scan_resident,
+    and what scan() uses when the loaded library has no gapped entry (the oracle); sized for fixtures, not for databases."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+    n, pen = len(data), int(max_penalty)
+    empty = np.empty((0, 4), np.int32)
+    if n == 0 or not len(reads):
+        return empty
+    n_gap = min(int(max_gap), KMM_MAX_GAP, (pen - 5) // 3) if pen >= 8 else 0
+    budget = pen // 6
+    text = np.concatenate([_BASE_CODE[data], np.full(PATTERN_MAX_LEN + KMM_MAX_GAP, 4, np.uint8)])
+    row_of = np.repeat(np.arange(len(row_off) - 1), np.diff(row_off))
+    room_all = row_off[row_of + 1] - row_off[0] - np.arange(n)              # bases from a start to the end of its sequence
+    found = []
+    for r, read in enumerate(reads):
+        fwd = _BASE_CODE[np.frombuffer(read.encode(), np.uint8)]
+        L = len(fwd)
+        if term > L:
+            continue
+        for strand in (0, 1):
+            P = fwd if strand == 0 else (3 - fwd[::-1])
+            # columns 0 .. GBAR - 1 pair on diagonal 0 in every alignment: more mismatches there than any form allows end a start
+            head = np.zeros(n, np.int32)
+            for j in range(min(GBAR, L)):
+                head += text[j:j + n] != P[j]
+            cand = np.nonzero((head <= budget) & (room_all >= L - n_gap))[0]
+            if not len(cand):
+                continue
+            W = text[cand[:, None] + np.arange(L + n_gap)]
+            room = room_all[cand]
+            A = W[:, :L] != P
+            ok = (A.sum(1) <= budget) & (room >= L) & ~A[:, L - term:].any(1)
+            below = np.concatenate([np.zeros((len(cand), 1), np.int32), np.cumsum(A, 1, dtype=np.int32)], 1)     # below[:, c]: A's before c
+            for g in range(1, n_gap + 1):
+                m = (pen - 5 - 3 * g) // 6
+                for kind, cols in (("D", L), ("I", L - g)):
+                    B = (W[:, g:g + L] != P) if kind == "D" else (W[:, :cols] != P[g:])
+                    above = np.concatenate([np.cumsum(B[:, ::-1], 1, dtype=np.int32)[:, ::-1], np.zeros((len(cand), 1), np.int32)], 1)
+                    c = np.arange(GBAR, (min(L - GBAR, L - term) if kind == "D" else cols - GBAR) + 1)
+                    if not len(c) or term > cols:
+                        continue
+                    fits = below[:, c] + above[:, c] <= m
+                    first = cols - term                                      # the term columns: first .. cols - 1
+                    if kind == "D":                                          # all of them right of the deletion (c <= first)
+                        fits &= (above[:, [first]] == 0) & (room >= L + g)[:, None]
+                    else:                                                    # right of c from B, left of it from A
+                        k = np.maximum(c, first)
+                        fits &= (below[:, k] == below[:, [first]]) & (above[:, k] == 0) & (room >= cols)[:, None]
+                    ok |= fits.any(1)
+            sel = cand[ok]
+            if len(sel):
+                rows = row_of[sel]
+                found.append(np.stack([rows, sel - (row_off[rows] - row_off[0]), np.full(len(sel), r), np.full(len(sel), strand)], 1))
+    if not found:
+        return empty
+    h = np.concatenate(found).astype(np.int32)
+    return h[np.lexsort((h[:, 3], h[:, 2], h[:, 1], h[:, 0]))]
 
 
 class TermTable:
@@ -152,7 +232,7 @@ def amplicons(forward, reverse, size_lo, size_hi):
 
 class off_targets(object):
     def __init__(self, primer_file, term_length, reference_file, PCR_product_size, mismatch_num, outfile, term_threshold,
-                 bowtie="bowtie2", nproc=20, targets="None", *, library: Library | None = None, device: int = 0, max_mismatch=None):
+                 bowtie="bowtie2", nproc=20, targets="None", *, library: Library | None = None, device: int = 0, max_mismatch=None, gaps=False):
         self.bowtie = bowtie                    # accepted for compatibility: no external mapper is run
         self.term_threshold = int(term_threshold)
         self.nproc = nproc
@@ -164,11 +244,16 @@ class off_targets(object):
         self.mismatch_num = mismatch_num        # bowtie's -N / -n: seed sensitivity only, the scan is exhaustive
         self.targets = targets
         self.max_mismatch = max_mismatch
+        self.gaps = bool(gaps)                  # admit bowtie2's one short gap (module docstring); off: the ungapped rule, as ever
         self._library, self._device = library, device
         self.stats = {}
 
     def _beside_primers(self, suffix):
         return Path(self.primer_file).parent.joinpath(Path(self.primer_file).stem).with_suffix(suffix)
+
+    def penalty_ceiling(self, length):
+        """What a read of `length` bases may lose with `gaps`: 6 per mismatch of --max-mismatch, else bowtie2's floor(0.6 + 0.6 L)."""
+        return 6 * self.max_mismatch if self.max_mismatch is not None else bowtie2_penalty_ceiling(length)
 
     # -- sites from the GPU ------------------------------------------------------------------------------------------------
     def scan(self, table: TermTable):
@@ -191,7 +276,22 @@ class off_targets(object):
             # scans the stored words (rounds 2-5 sent the ASCII text with every call)
             ctx.seq_load(data, row_off)
             budgets = {}
-            for i in usable:
+            for i in usable if self.gaps else ():           # reads by penalty ceiling: one gapped scan each
+                budgets.setdefault(self.penalty_ceiling(len(seqs[i])), []).append(i)
+            for pen, members in budgets.items():
+                if lib.gapscan:
+                    codes = iupac.MASK_LUT[np.frombuffer("".join(seqs[i].upper() for i in members).encode(), np.uint8)]
+                    off = np.zeros(len(members) + 1, np.int32)
+                    np.cumsum([len(seqs[i]) for i in members], out=off[1:])
+                    h = ctx.kmm_gap_scan_resident(codes, off, pen, KMM_MAX_GAP, self.term_threshold)
+                else:                                       # the oracle library of the CPU tests: the host form of the rule
+                    h = gap_scan_host(data, row_off, [seqs[i].upper() for i in members], pen, KMM_MAX_GAP, self.term_threshold)
+                if len(h):
+                    h = h.copy()
+                    h[:, 2] = np.asarray(members, np.int32)[h[:, 2]]
+                    found.append(h)
+            budgets = {}
+            for i in () if self.gaps else usable:
                 budgets.setdefault(self.max_mismatch if self.max_mismatch is not None else bowtie2_mismatch_budget(len(seqs[i])), []).append(i)
             for budget, members in budgets.items():
                 codes = iupac.MASK_LUT[np.frombuffer("".join(seqs[i].upper() for i in members).encode(), np.uint8)]
@@ -270,6 +370,8 @@ def parse_args(argv=None):
     p.add_argument("-d", "--dict", type=str, default="None", metavar="<str>", help="Dictionary of targets sequences, binary format (prepare_fa_pickle.py).")
     p.add_argument("-o", "--out", type=str, required=True, metavar="<file>", help="Output file: Prodcut of PCR product with primers.")
     p.add_argument("--max-mismatch", type=int, default=None, help="mismatches per alignment (default: bowtie2's budget floor((0.6 + 0.6 L) / 6))")
+    p.add_argument("--gaps", action="store_true", help="also admit bowtie2's one short gap (5 + 3 g for g <= 4 bases, at least 4 bases from "
+                                                       "the read ends) within the same minimum score; default: ungapped")
     p.add_argument("--device", type=int, default=0)
     return p.parse_args(argv)
 
@@ -281,6 +383,6 @@ def main(argv=None):
     e1 = time.time()
     off_targets(primer_file=args.input, term_length=args.len, reference_file=args.ref, PCR_product_size=args.size,
                 mismatch_num=args.seedmms, outfile=args.out, term_threshold=args.term, bowtie=args.bowtie, nproc=args.proc,
-                targets=args.dict, device=args.device, max_mismatch=args.max_mismatch).run()
+                targets=args.dict, device=args.device, max_mismatch=args.max_mismatch, gaps=args.gaps).run()
     e2 = time.time()
     print("INFO {} Total times: {}".format(time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(time.time())), round(float(e2 - e1), 2)))

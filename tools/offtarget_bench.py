@@ -6,6 +6,10 @@ and term length: the device stages (event times), the whole run() of each path, 
 wrote the same three files.  One JSON line per measurement on stdout.
 
     python tools/offtarget_bench.py --bases 1e8 1e9 --terms 9 18
+
+--gaps: every device run is followed by one under the gapped rule (validate.py: `--gaps`) on the same input, alternating; the record
+then carries both (`device`, `device_gaps`), the scan time of every run (`scan_ms`, `scan_ms_gaps`) and, with the host path, whether
+the gapped files agree too (`equal_gaps`).
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--size", default="100,1500")
     ap.add_argument("--repeat", type=int, default=2, help="device runs per point (the first warms the process up)")
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--gaps", action="store_true", help="measure the gapped rule beside the ungapped one, alternating runs")
     a = ap.parse_args()
     import torch  # noqa: F401  (one HIP runtime per process: torch's, as in the GPU suite)
     from multiprime_amd._abi import Library
@@ -47,12 +52,18 @@ def main():
             made = time.time() - t0
             for term in a.terms:
                 rec = {"bases": n_rows * a.row_len, "rows": n_rows, "term": term, "size": a.size, "primers": a.primers, "make_input_s": round(made, 2)}
+                scan_ms = {False: [], True: []}
                 for rep in range(a.repeat):
-                    app = off_targets(primer_file=pf, term_length=term, reference_file=bf, PCR_product_size=a.size, outfile=os.path.join(td, "dev.out"),
-                                      library=lib, join="device")
-                    with contextlib.redirect_stdout(io.StringIO()):
-                        app.run()
-                rec["device"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in app.stats.items()}
+                    for gaps in (False, True) if a.gaps else (False,):
+                        app = off_targets(primer_file=pf, term_length=term, reference_file=bf, PCR_product_size=a.size,
+                                          outfile=os.path.join(td, "gap.out" if gaps else "dev.out"), library=lib, join="device", gaps=gaps)
+                        with contextlib.redirect_stdout(io.StringIO()):
+                            app.run()
+                        scan_ms[gaps].append(round(app.stats["scan_ms"], 3))
+                        rec["device_gaps" if gaps else "device"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in app.stats.items()}
+                rec["scan_ms"] = scan_ms[False]
+                if a.gaps:
+                    rec["scan_ms_gaps"] = scan_ms[True]
                 if not a.no_host:
                     host = off_targets(primer_file=pf, term_length=term, reference_file=bf, PCR_product_size=a.size, outfile=os.path.join(td, "host.out"),
                                        library=lib, join="host")
@@ -60,8 +71,14 @@ def main():
                         host.run()
                     rec["host"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in host.stats.items()}
                     rec["equal"] = files(os.path.join(td, "dev.out")) == files(os.path.join(td, "host.out"))
+                    if a.gaps:
+                        host = off_targets(primer_file=pf, term_length=term, reference_file=bf, PCR_product_size=a.size,
+                                           outfile=os.path.join(td, "hostgap.out"), library=lib, join="host", gaps=True)
+                        with contextlib.redirect_stdout(io.StringIO()):
+                            host.run()
+                        rec["equal_gaps"] = files(os.path.join(td, "gap.out")) == files(os.path.join(td, "hostgap.out"))
                 print(json.dumps(rec), flush=True)
-                if not rec.get("equal", True):
+                if not (rec.get("equal", True) and rec.get("equal_gaps", True)):
                     sys.exit(1)
 
 

@@ -179,5 +179,10 @@ offtarget)       # profiles/offtarget_scale.txt: the off-target screen, device p
   set -o pipefail
   timeout -k 10 300 python -m pytest tests/test_offtarget_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
   timeout -k 10 1500 python tools/offtarget_bench.py --bases 1e8 1e9 --terms 9 18 2>&1 | tee $O/offtarget_scale.txt ;;
+gapscan)         # profiles/gapscan_scale.txt: the scan under the gapped rule (--gaps) against the ungapped one, same store, alternating runs, 10^8 bases
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 600 python -m pytest tests/test_gapscan_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 900 python tools/offtarget_bench.py --gaps --bases 1e8 --terms 18 --repeat 4 --no-host 2>&1 | tee $O/gapscan_scale.txt ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
