@@ -107,6 +107,25 @@ GAP_SYMBOLS = [
 KMM_MAX_GAP = 4                     # MP_KMM_MAX_GAP
 
 
+class AnchorParams(C.Structure):
+    """mp_anchor_params (include/mprime_anchor.h)."""
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("band", C.c_int32),
+                ("min_identity_permille", C.c_int32)]
+
+
+# include/mprime_anchor.h: anchored alignment on the device (csrc/anchor.hip) — exported by libmprime_hip.so only and bound where a library
+# has them; the checker of these calls is the plain restatement of the rule in tests/anchor_ref.py
+ANCHOR_SYMBOLS = [
+    ("mp_anchor_set", C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, C.POINTER(AnchorParams)]),
+    ("mp_anchor_align", C.c_int, [_p, C.c_int32, _p, _p, C.c_int32, _p, _p, _p, _p]),
+    ("mp_anchor_stats", C.c_int, [_p, _p, _p]),
+]
+ANCHOR_MAX_LEN = 32767              # MP_ANCHOR_MAX_LEN
+ANCHOR_MAX_BAND = 255               # MP_ANCHOR_MAX_BAND
+ANCHOR_MAX_PARAM = 4095             # MP_ANCHOR_MAX_PARAM
+ANCHOR_META = 10                    # MP_ANCHOR_META
+
+
 def prefer_staged_copies():
     """For the drop-in command lines, called before anything starts the HIP runtime: read-backs into ordinary numpy arrays go
     through the runtime's staging buffers instead of page-locking the array for one use (GPU_PINNED_MIN_XFER_SIZE = 256 MiB: the
@@ -198,7 +217,11 @@ class Library:
         self.gapscan = all(hasattr(self.dll, name) for name, _, _ in GAP_SYMBOLS)
         if self.backend == "hip" and not self.gapscan:
             raise MprimeError(-2, f"{path} lacks the gapped-scan entry points of include/mprime_offtarget.h: rebuild it")
-        for name, res, args in (OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []):
+        self.anchor = all(hasattr(self.dll, name) for name, _, _ in ANCHOR_SYMBOLS)
+        if self.backend == "hip" and not self.anchor:
+            raise MprimeError(-2, f"{path} lacks the anchored-alignment entry points of include/mprime_anchor.h: rebuild it")
+        for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
+                                (ANCHOR_SYMBOLS if self.anchor else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -731,6 +754,50 @@ class Context:
         self._ck(self.d.mp_offtarget_stats(self.h, _ptr(ms), _ptr(counts)))
         return (dict(zip(("scan_ms", "reduce_ms", "join_ms", "call_ms"), ms.tolist())),
                 dict(zip(("hits", "forward_sites", "reverse_sites", "products", "forward_genes", "reverse_genes", "both_genes"), counts.tolist())))
+
+    # include/mprime_anchor.h
+    def _need_anchor(self):
+        if not self.lib.anchor:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_anchor.h (libmprime_hip.so does)")
+
+    def anchor_set(self, anchor, col, width: int, band: int = 32, match: int = 5, mismatch: int = 4, gap_open: int = 10, gap_extend: int = 2,
+                   min_identity_permille: int = 500):
+        """Keep the anchor (upper-case letters, bytes or uint8 array) and its seed columns in the context (mp_anchor_set)."""
+        self._need_anchor()
+        codes = np.ascontiguousarray(np.frombuffer(anchor, np.uint8) if isinstance(anchor, (bytes, bytearray)) else anchor, dtype=np.uint8)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        par = AnchorParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(band), int(min_identity_permille))
+        self._ck(self.d.mp_anchor_set(self.h, _ptr(codes), len(codes), _ptr(col), int(width), C.byref(par)))
+        self.anchor_n, self.anchor_width = len(codes), int(width)
+
+    def anchor_align(self, data, off, want_ops: bool = False):
+        """(rows uint8 [n][width], meta int32 [n][ANCHOR_META], ops): the queries data[off[q]:off[q+1]] placed on the anchor.  ops: a list
+        of byte strings over M / D / I when asked for, else None."""
+        self._need_anchor()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        nq = len(off) - 1
+        rows = np.empty((max(nq, 1), self.anchor_width), np.uint8)
+        meta = np.zeros((max(nq, 1), ANCHOR_META), np.int32)
+        ops_off = ops_buf = None
+        if want_ops:
+            ops_off = np.ascontiguousarray(off + np.arange(nq + 1, dtype=np.int64) * self.anchor_n)       # a slot of m + n bytes per query
+            ops_buf = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+        self._ck(self.d.mp_anchor_align(self.h, nq, _ptr(data), _ptr(off), int(want_ops), _ptr(rows), _ptr(meta), _ptr(ops_buf), _ptr(ops_off)))
+        ops = None
+        if want_ops:                               # right-aligned in its slot, m + n_del letters
+            length = np.diff(off) + meta[:nq, 4]
+            ops = [ops_buf[int(ops_off[q + 1]) - int(length[q]): int(ops_off[q + 1])].tobytes() if meta[q, 0] != -(1 << 31) else b""
+                   for q in range(nq)]
+        return rows[:nq], meta[:nq], ops
+
+    def anchor_stats(self):
+        """Of the last anchor_align: ({vote, dp, trace, readback, call}_ms, {batches, cells, traceback_bytes})."""
+        self._need_anchor()
+        ms, counts = np.zeros(5, np.float64), np.zeros(3, np.int64)
+        self._ck(self.d.mp_anchor_stats(self.h, _ptr(ms), _ptr(counts)))
+        return (dict(zip(("vote_ms", "dp_ms", "trace_ms", "readback_ms", "call_ms"), ms.tolist())),
+                dict(zip(("batches", "cells", "traceback_bytes"), counts.tolist())))
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

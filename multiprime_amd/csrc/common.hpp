@@ -284,6 +284,15 @@ struct mp_ctx {
     std::vector<uint8_t> ot_key;
     double ot_ms[4] = {0, 0, 0, 0};
     int64_t ot_counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    // anchored alignment (anchor.hip, include/mprime_anchor.h): the anchor of mp_anchor_set and the times / counts of the last mp_anchor_align
+    uint8_t *an_code = nullptr;              // [an_n] 0..3 = A, C, G, T, 4 = anything else
+    uint32_t *an_kmer = nullptr;             // [an_n] 2-bit code of the 12-mer starting at j, kEmpty where it does not exist
+    int32_t *an_table = nullptr;             // [an_slots] open addressing: anchor position, -1 = empty
+    int32_t *an_col = nullptr, *an_colinv = nullptr;    // [an_n] seed column of a position / [an_L] position of a column, -1 = none
+    int32_t an_n = 0, an_L = 0, an_slots = 0;
+    int32_t an_par[6] = {0, 0, 0, 0, 0, 0};  // mp_anchor_params
+    double an_ms[5] = {0, 0, 0, 0, 0};
+    int64_t an_counts[3] = {0, 0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run
@@ -392,6 +401,7 @@ void free_slide(mp_ctx *c);
 void free_comm(mp_ctx *c);
 void free_unique(mp_ctx *c);
 void free_seq(mp_ctx *c);        // scan.hip
+void free_anchor(mp_ctx *c);     // anchor.hip
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

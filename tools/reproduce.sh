@@ -184,5 +184,11 @@ gapscan)         # profiles/gapscan_scale.txt: the scan under the gapped rule (-
   set -o pipefail
   timeout -k 10 600 python -m pytest tests/test_gapscan_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
   timeout -k 10 900 python tools/offtarget_bench.py --gaps --bases 1e8 --terms 18 --repeat 4 --no-host 2>&1 | tee $O/gapscan_scale.txt ;;
+anchor_scale)    # profiles/anchor_scale.txt: anchored alignment, 10^5 / 10^6 queries of 1 kb, W = 32 / 128 in alternating runs; then the kernel trace in a run of its own
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_anchor_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 900 python tools/anchor_bench.py --out $O/anchor_scale.txt &&
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_anchor -- python tools/anchor_bench.py --queries 100000 --repeats 1 2>&1 | tail -5 ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
