@@ -126,6 +126,23 @@ ANCHOR_MAX_PARAM = 4095             # MP_ANCHOR_MAX_PARAM
 ANCHOR_META = 10                    # MP_ANCHOR_META
 
 
+class ClusterParams(C.Structure):
+    """mp_cluster_params (include/mprime_cluster.h)."""
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("band", C.c_int32),
+                ("identity_permille", C.c_int32), ("min_votes", C.c_int32)]
+
+
+# include/mprime_cluster.h: clustering by identity on the device (csrc/cluster.hip) — exported by libmprime_hip.so only; the checker of
+# these calls is the plain restatement of the rule in tests/cluster_ref.py
+CLUSTER_SYMBOLS = [
+    ("mp_cluster_load", C.c_int, [_p, C.c_int32, _p, _p]),
+    ("mp_cluster_pairs", C.c_int, [_p, C.c_int64, _p, _p, C.POINTER(ClusterParams), _p]),
+    ("mp_cluster_greedy", C.c_int, [_p, C.POINTER(ClusterParams), _p, _p, _p, C.POINTER(C.c_int32)]),
+    ("mp_cluster_stats", C.c_int, [_p, _p, _p]),
+]
+CLUSTER_PAIR = 5                    # MP_CLUSTER_PAIR
+
+
 def prefer_staged_copies():
     """For the drop-in command lines, called before anything starts the HIP runtime: read-backs into ordinary numpy arrays go
     through the runtime's staging buffers instead of page-locking the array for one use (GPU_PINNED_MIN_XFER_SIZE = 256 MiB: the
@@ -220,8 +237,11 @@ class Library:
         self.anchor = all(hasattr(self.dll, name) for name, _, _ in ANCHOR_SYMBOLS)
         if self.backend == "hip" and not self.anchor:
             raise MprimeError(-2, f"{path} lacks the anchored-alignment entry points of include/mprime_anchor.h: rebuild it")
+        self.cluster = all(hasattr(self.dll, name) for name, _, _ in CLUSTER_SYMBOLS)
+        if self.backend == "hip" and not self.cluster:
+            raise MprimeError(-2, f"{path} lacks the clustering entry points of include/mprime_cluster.h: rebuild it")
         for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
-                                (ANCHOR_SYMBOLS if self.anchor else [])):
+                                (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -798,6 +818,53 @@ class Context:
         self._ck(self.d.mp_anchor_stats(self.h, _ptr(ms), _ptr(counts)))
         return (dict(zip(("vote_ms", "dp_ms", "trace_ms", "readback_ms", "call_ms"), ms.tolist())),
                 dict(zip(("batches", "cells", "traceback_bytes"), counts.tolist())))
+
+    # include/mprime_cluster.h
+    def _need_cluster(self):
+        if not self.lib.cluster:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_cluster.h (libmprime_hip.so does)")
+
+    def cluster_load(self, data, off):
+        """Make the sequences data[off[i]:off[i+1]] resident (mp_cluster_load)."""
+        self._need_cluster()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        self._ck(self.d.mp_cluster_load(self.h, len(off) - 1, _ptr(data), _ptr(off)))
+        self.cluster_n = len(off) - 1
+
+    @staticmethod
+    def _cluster_params(band, identity_permille, min_votes, match, mismatch, gap_open, gap_extend):
+        return ClusterParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(band), int(identity_permille), int(min_votes))
+
+    def cluster_pairs(self, q_idx, r_idx, band: int = 32, identity_permille: int = 800, min_votes: int = 1, match: int = 5, mismatch: int = 4,
+                      gap_open: int = 10, gap_extend: int = 2) -> np.ndarray:
+        """int32 [n_pairs][CLUSTER_PAIR] = votes, d0, score, n_match, status of query q_idx[p] against anchor r_idx[p] (mp_cluster_pairs)."""
+        self._need_cluster()
+        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
+        r_idx = np.ascontiguousarray(r_idx, dtype=np.int32)
+        out = np.zeros((max(len(q_idx), 1), CLUSTER_PAIR), np.int32)
+        par = self._cluster_params(band, identity_permille, min_votes, match, mismatch, gap_open, gap_extend)
+        self._ck(self.d.mp_cluster_pairs(self.h, len(q_idx), _ptr(q_idx), _ptr(r_idx), C.byref(par), _ptr(out)))
+        return out[: len(q_idx)]
+
+    def cluster_greedy(self, band: int = 32, identity_permille: int = 800, min_votes: int = 1, match: int = 5, mismatch: int = 4,
+                       gap_open: int = 10, gap_extend: int = 2):
+        """(cluster_of int32 [n], rep_of_cluster int32 [n_clusters], n_match_of int32 [n]) of the resident sequences (mp_cluster_greedy)."""
+        self._need_cluster()
+        n = getattr(self, "cluster_n", 0)
+        cluster_of, rep, n_match = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        nc = C.c_int32(0)
+        par = self._cluster_params(band, identity_permille, min_votes, match, mismatch, gap_open, gap_extend)
+        self._ck(self.d.mp_cluster_greedy(self.h, C.byref(par), _ptr(cluster_of), _ptr(rep), _ptr(n_match), C.byref(nc)))
+        return cluster_of[:n], rep[: nc.value], n_match[:n]
+
+    def cluster_stats(self):
+        """Of the last cluster_greedy / cluster_pairs: ({index, seed, dp, resolve, call}_ms, {rounds, pairs, cells})."""
+        self._need_cluster()
+        ms, counts = np.zeros(5, np.float64), np.zeros(3, np.int64)
+        self._ck(self.d.mp_cluster_stats(self.h, _ptr(ms), _ptr(counts)))
+        return (dict(zip(("index_ms", "seed_ms", "dp_ms", "resolve_ms", "call_ms"), ms.tolist())),
+                dict(zip(("rounds", "pairs", "cells"), counts.tolist())))
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

@@ -14,6 +14,7 @@
 //                        gets its parallelism from the number of queries), writes the letters in anchor space, the meta record and the ops
 //   anchor_emit_kernel   expands anchor space to the seed's L columns: 16 row bytes per lane, one 128-bit store each
 #include "common.hpp"
+#include "seedword.hpp"
 #include "../../include/mprime_anchor.h"
 
 namespace mp {
@@ -24,12 +25,7 @@ constexpr int kNeg = -(1 << 30);               // "no such cell": below every re
 constexpr int kNoPath = -(3 << 28);            // a best end score below this was never fed by row 0 (mprime_anchor.h: MP_ANCHOR_MAX_PARAM)
 constexpr int kWord = MP_ANCHOR_WORD;
 
-__host__ __device__ inline int base_code(uint8_t ch) {
-    ch &= 0xDF;                                // upper case
-    return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
-}
 __host__ __device__ inline uint8_t upper_letter(uint8_t ch) { return ch >= 'a' && ch <= 'z' ? (uint8_t)(ch - 32) : ch; }
-__host__ __device__ inline uint32_t word_hash(uint32_t kmer, int log2_slots) { return (kmer * 2654435761u) >> (32 - log2_slots); }
 
 // ---- votes --------------------------------------------------------------------------------------------------------------------------
 // better(a, b): diagonal vote (ca, da) beats (cb, db) — more votes, then the smaller |d|, then the smaller d

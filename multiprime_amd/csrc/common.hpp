@@ -293,6 +293,14 @@ struct mp_ctx {
     int32_t an_par[6] = {0, 0, 0, 0, 0, 0};  // mp_anchor_params
     double an_ms[5] = {0, 0, 0, 0, 0};
     int64_t an_counts[3] = {0, 0, 0};
+    // clustering by identity (cluster.hip, include/mprime_cluster.h): the sequences of mp_cluster_load and the times / counts of the last call
+    uint8_t *cl_code = nullptr;              // [cl_total] 0..3 = A, C, G, T, 4 = anything else, sequences back to back
+    int64_t *cl_off = nullptr;               // [cl_n + 1]
+    int32_t cl_n = 0;
+    size_t cl_total = 0;
+    std::vector<int64_t> cl_off_host;
+    double cl_ms[5] = {0, 0, 0, 0, 0};
+    int64_t cl_counts[3] = {0, 0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run
@@ -402,6 +410,7 @@ void free_comm(mp_ctx *c);
 void free_unique(mp_ctx *c);
 void free_seq(mp_ctx *c);        // scan.hip
 void free_anchor(mp_ctx *c);     // anchor.hip
+void free_cluster(mp_ctx *c);    // cluster.hip
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

@@ -190,5 +190,11 @@ anchor_scale)    # profiles/anchor_scale.txt: anchored alignment, 10^5 / 10^6 qu
   timeout -k 10 300 python -m pytest tests/test_anchor_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
   timeout -k 10 900 python tools/anchor_bench.py --out $O/anchor_scale.txt &&
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_anchor -- python tools/anchor_bench.py --queries 100000 --repeats 1 2>&1 | tail -5 ;;
+cluster)         # profiles/cluster_scale.txt: clustering by identity, 10^4 .. 10^6 records of 1 kb, -c 0.8 / -c 1 in alternating runs; then the kernel trace in a run of its own
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_cluster_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 1100 python tools/cluster_bench.py --out $O/cluster_scale.txt &&
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_cluster -- python tools/cluster_bench.py --records 100000 --repeats 0 2>&1 | tail -5 ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
