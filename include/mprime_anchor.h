@@ -45,8 +45,8 @@
  * On request the op string over M (pair), D (anchor column skipped), I (query base dropped), first to last aligned position:
  * m + n_del letters.
  *
- * Limits: query and anchor length 1 .. MP_ANCHOR_MAX_LEN each; scores are int32.  Not attempted: a seed alignment from nothing,
- * re-estimating the anchor from the added rows, reverse-complement queries, several GPUs.
+ * Limits: query and anchor length 1 .. MP_ANCHOR_MAX_LEN each; scores are int32.  A seed alignment from nothing and an
+ * anchor re-estimated from the added rows are mprime_star.h's.  Not attempted: reverse-complement queries, several GPUs.
  */
 #ifndef MPRIME_ANCHOR_H
 #define MPRIME_ANCHOR_H

@@ -142,6 +142,20 @@ CLUSTER_SYMBOLS = [
 ]
 CLUSTER_PAIR = 5                    # MP_CLUSTER_PAIR
 
+# include/mprime_star.h: the star alignment on the device (csrc/star.hip) — exported by libmprime_hip.so only; the checker of these calls
+# is the plain restatement of the rule in tests/star_ref.py
+STAR_SYMBOLS = [
+    ("mp_star_load", C.c_int, [_p, C.c_int32, _p, _p]),
+    ("mp_star_round", C.c_int, [_p, _p, C.c_int32, C.POINTER(AnchorParams), _p, _p, C.POINTER(C.c_int32)]),
+    ("mp_star_rows", C.c_int, [_p, _p]),
+    ("mp_star_counts", C.c_int, [_p, _p]),
+    ("mp_star_stats", C.c_int, [_p, _p, _p]),
+    ("mp_star_free", C.c_int, [_p]),
+]
+STAR_MAX_ROUNDS = 8                 # MP_STAR_MAX_ROUNDS
+STAR_META = ANCHOR_META + 1         # MP_STAR_META
+STAR_COUNTS = 6                     # MP_STAR_COUNTS
+
 
 def prefer_staged_copies():
     """For the drop-in command lines, called before anything starts the HIP runtime: read-backs into ordinary numpy arrays go
@@ -240,8 +254,12 @@ class Library:
         self.cluster = all(hasattr(self.dll, name) for name, _, _ in CLUSTER_SYMBOLS)
         if self.backend == "hip" and not self.cluster:
             raise MprimeError(-2, f"{path} lacks the clustering entry points of include/mprime_cluster.h: rebuild it")
+        self.star = all(hasattr(self.dll, name) for name, _, _ in STAR_SYMBOLS)
+        if self.backend == "hip" and not self.star:
+            raise MprimeError(-2, f"{path} lacks the star-alignment entry points of include/mprime_star.h: rebuild it")
         for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
-                                (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else [])):
+                                (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
+                                (STAR_SYMBOLS if self.star else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -865,6 +883,63 @@ class Context:
         self._ck(self.d.mp_cluster_stats(self.h, _ptr(ms), _ptr(counts)))
         return (dict(zip(("index_ms", "seed_ms", "dp_ms", "resolve_ms", "call_ms"), ms.tolist())),
                 dict(zip(("rounds", "pairs", "cells"), counts.tolist())))
+
+    # include/mprime_star.h
+    def _need_star(self):
+        if not self.lib.star:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_star.h (libmprime_hip.so does)")
+
+    def star_load(self, data, off):
+        """Make the records data[off[q]:off[q+1]] resident (mp_star_load)."""
+        self._need_star()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        self.star_n = 0
+        self._ck(self.d.mp_star_load(self.h, len(off) - 1, _ptr(data), _ptr(off)))
+        self.star_n = len(off) - 1
+
+    def star_round(self, anchor, band: int = 32, match: int = 5, mismatch: int = 4, gap_open: int = 10, gap_extend: int = 2,
+                   min_identity_permille: int = 500):
+        """One round against `anchor` (mp_star_round): (meta int32 [n_records][STAR_META], ins int32 [n + 1], width)."""
+        self._need_star()
+        codes = np.ascontiguousarray(np.frombuffer(anchor, np.uint8) if isinstance(anchor, (bytes, bytearray)) else anchor, dtype=np.uint8)
+        n_rec = getattr(self, "star_n", 0)
+        meta = np.zeros((max(n_rec, 1), STAR_META), np.int32)
+        ins = np.zeros(len(codes) + 1, np.int32)
+        width = C.c_int32(0)
+        par = AnchorParams(int(match), int(mismatch), int(gap_open), int(gap_extend), int(band), int(min_identity_permille))
+        self.star_width = 0
+        self._ck(self.d.mp_star_round(self.h, _ptr(codes), len(codes), C.byref(par), _ptr(meta), _ptr(ins), C.byref(width)))
+        self.star_width = int(width.value)
+        return meta[:n_rec], ins, self.star_width
+
+    def star_rows(self) -> np.ndarray:
+        """uint8 [n_records][width]: the rows of the last round, all-gap for the unplaced records (mp_star_rows)."""
+        self._need_star()
+        rows = np.empty((max(getattr(self, "star_n", 0), 1), max(getattr(self, "star_width", 0), 1)), np.uint8)
+        self._ck(self.d.mp_star_rows(self.h, _ptr(rows)))
+        return rows[: self.star_n]
+
+    def star_counts(self) -> np.ndarray:
+        """int32 [width][STAR_COUNTS]: A, C, G, T, other letter, gap per column over the placed rows of the last round (mp_star_counts)."""
+        self._need_star()
+        counts = np.zeros((max(getattr(self, "star_width", 0), 1), STAR_COUNTS), np.int32)
+        self._ck(self.d.mp_star_counts(self.h, _ptr(counts)))
+        return counts[: self.star_width]
+
+    def star_stats(self):
+        """Of the last star_round: ({vote, dp, trace, profile, write, count, readback, call}_ms, {batches, cells, realigned,
+        traceback_bytes, store_bytes, placed})."""
+        self._need_star()
+        ms, counts = np.zeros(8, np.float64), np.zeros(6, np.int64)
+        self._ck(self.d.mp_star_stats(self.h, _ptr(ms), _ptr(counts)))
+        return (dict(zip(("vote_ms", "dp_ms", "trace_ms", "profile_ms", "write_ms", "count_ms", "readback_ms", "call_ms"), ms.tolist())),
+                dict(zip(("batches", "cells", "realigned", "traceback_bytes", "store_bytes", "placed"), counts.tolist())))
+
+    def star_free(self):
+        self._need_star()
+        self._ck(self.d.mp_star_free(self.h))
+        self.star_n = self.star_width = 0
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

@@ -1,236 +1,11 @@
 // anchor.hip — anchored alignment (include/mprime_anchor.h): every query is placed on the anchor of a seed alignment by a banded
-// affine-gap (Gotoh) alignment around a voted seed diagonal.  Three kernels per batch of queries:
-//   anchor_vote_kernel   one wavefront per query: its 12-mers are looked up in the anchor's open-addressing table, the votes per
-//                        diagonal counted in an LDS histogram (two 16-bit counters per word), d0 chosen by a wave reduction
-//   anchor_dp_kernel     one wavefront per query, lanes own the band's diagonals (R = 1, 2, 4 or 8 neighbouring diagonals per lane for
-//                        2W + 1 <= 64 R).  ANTI-DIAGONAL sweep: at step s the cells with i + j = s are computed; cell (i, j) on diagonal
-//                        d reads its left cell (i, j-1) from diagonal d - 1 and its upper cell (i-1, j) from diagonal d + 1, both
-//                        computed at step s - 1, and its diagonal cell from its own registers — no dependency inside a step, so no
-//                        scan; a lane is busy every other step.  Four predecessor bits per cell (H source 2, E opened, F opened)
-//                        are collected eight rows to a word per diagonal and stored to the traceback buffer in HBM.  Anchor codes
-//                        (shared by the workgroup's waves) and the wave's query codes sit in LDS; the pair score is two compares on
-//                        the codes, so no per-letter profile rows are kept.
-//   anchor_trace_kernel  one lane per query walks the bits from the end cell (a chain of dependent loads: latency-bound, so it
-//                        gets its parallelism from the number of queries), writes the letters in anchor space, the meta record and the ops
+// affine-gap (Gotoh) alignment around a voted seed diagonal.  The vote, sweep and traceback kernels are those of anchorcore.hpp; here:
 //   anchor_emit_kernel   expands anchor space to the seed's L columns: 16 row bytes per lane, one 128-bit store each
-#include "common.hpp"
-#include "seedword.hpp"
-#include "../../include/mprime_anchor.h"
+#include "anchorcore.hpp"
 
 namespace mp {
 
 namespace {
-
-constexpr int kNeg = -(1 << 30);               // "no such cell": below every real score by more than any real score can gain
-constexpr int kNoPath = -(3 << 28);            // a best end score below this was never fed by row 0 (mprime_anchor.h: MP_ANCHOR_MAX_PARAM)
-constexpr int kWord = MP_ANCHOR_WORD;
-
-__host__ __device__ inline uint8_t upper_letter(uint8_t ch) { return ch >= 'a' && ch <= 'z' ? (uint8_t)(ch - 32) : ch; }
-
-// ---- votes --------------------------------------------------------------------------------------------------------------------------
-// better(a, b): diagonal vote (ca, da) beats (cb, db) — more votes, then the smaller |d|, then the smaller d
-__device__ inline bool vote_better(int ca, int da, int cb, int db) {
-    if (ca != cb) return ca > cb;
-    const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
-    if (aa != ab) return aa < ab;
-    return da < db;
-}
-
-__global__ __launch_bounds__(64) void anchor_vote_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict__ off, int n,
-                                                          const uint32_t *__restrict__ akmer, const int32_t *__restrict__ table, int log2_slots,
-                                                          int32_t *__restrict__ d0_out) {
-    extern __shared__ uint32_t hist[];         // bin b = d + m (1 .. m + n - 1): counter (b & 1) of word b >> 1
-    const int q = blockIdx.x, lane = threadIdx.x;
-    const uint8_t *qb = bytes + off[q];
-    const int m = (int)(off[q + 1] - off[q]);
-    const int words = (m + n) / 2 + 1;
-    for (int x = lane; x < words; x += 64) hist[x] = 0;
-    __syncthreads();
-    const uint32_t mask = (1u << log2_slots) - 1;
-    for (int i = lane; i + kWord <= m && n >= kWord; i += 64) {
-        uint32_t kmer = 0;
-        bool ok = true;
-        for (int x = 0; x < kWord; x++) {
-            const int cd = base_code(qb[i + x]);
-            ok = ok && cd < 4;
-            kmer = (kmer << 2) | (uint32_t)(cd & 3);
-        }
-        if (!ok) continue;
-        uint32_t slot = word_hash(kmer, log2_slots);
-        for (int32_t j; (j = table[slot]) >= 0; slot = (slot + 1) & mask)
-            if (akmer[j] == kmer) {
-                const int b = j - i + m;
-                atomicAdd(&hist[b >> 1], (b & 1) ? 65536u : 1u);
-            }
-    }
-    __syncthreads();
-    int best_c = 0, best_d = 0;
-    for (int b = 1 + lane; b <= m + n - 1; b += 64) {
-        const int cnt = (int)((hist[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu);
-        if (cnt > 0 && (best_c == 0 || vote_better(cnt, b - m, best_c, best_d))) { best_c = cnt; best_d = b - m; }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const int oc = __shfl_xor(best_c, sh), od = __shfl_xor(best_d, sh);
-        if (oc > 0 && (best_c == 0 || vote_better(oc, od, best_c, best_d))) { best_c = oc; best_d = od; }
-    }
-    if (lane == 0) d0_out[q] = best_c > 0 ? best_d : min(max(0, -m), n);
-}
-
-// ---- the banded Gotoh sweep ----------------------------------------------------------------------------------------------------------
-// Traceback bits of cell (i, t), i = 1 .. m, t = diagonal index inside the band: nibble (i - 1) & 7 of word tb[tb_off[q] + ((i - 1) >> 3) *
-// 64 R + t]; bits 0-1: H came from 0 the diagonal, 1 E, 2 F (3: the cell lies outside the matrix); bit 2: E opened here; bit 3: F opened here.
-template <int R>
-__global__ __launch_bounds__(256) void anchor_dp_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict__ off, int nq,
-                                                         const int32_t *__restrict__ d0v, const uint8_t *__restrict__ acode, int n, int W, int match,
-                                                         int mismatch, int open_ext, int ext, int mstride, uint32_t *__restrict__ tb,
-                                                         const int64_t *__restrict__ tb_off, int32_t *__restrict__ end_out) {
-    extern __shared__ uint8_t lds[];           // [npad] anchor codes, then [mstride] query codes per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    const int npad = (n + 15) & ~15;
-    for (int x = threadIdx.x; x < n; x += blockDim.x) lds[x] = acode[x];
-    const int q = blockIdx.x * wpb + wave;
-    uint8_t *qc = lds + npad + wave * mstride;
-    int m = 0;
-    if (q < nq) {
-        const uint8_t *qb = bytes + off[q];
-        m = (int)(off[q + 1] - off[q]);
-        for (int x = lane; x < m; x += 64) qc[x] = (uint8_t)base_code(qb[x]);
-    }
-    __syncthreads();                           // (the only barrier: what follows is per wave)
-    if (q >= nq) return;
-    const int B = 2 * W + 1, dlo = d0v[q] - W, Bpad = 64 * R;
-    uint32_t *tbq = tb + tb_off[q];
-    int H[R], E[R], F[R];
-    uint32_t acc[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int t = lane * R + r, d = dlo + t;
-        H[r] = (t < B && d >= 0 && d <= n) ? 0 : kNeg;          // the row-0 cell of the diagonal
-        E[r] = F[r] = kNeg;
-        acc[r] = 0;
-    }
-    const int s_end = 2 * m + dlo + B - 1;
-    for (int s = 2 + dlo; s <= s_end; s++) {
-        // the neighbouring lanes' edge diagonals as of step s - 1
-        int hl_edge = __shfl_up(H[R - 1], 1), el_edge = __shfl_up(E[R - 1], 1);
-        int hu_edge = __shfl_down(H[0], 1), fu_edge = __shfl_down(F[0], 1);
-        if (lane == 0) hl_edge = el_edge = kNeg;
-        if (lane == 63) hu_edge = fu_edge = kNeg;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int t = lane * R + r, d = dlo + t, two_i = s - d;
-            if ((two_i & 1) || two_i < 2 || two_i > 2 * m || t >= B) continue;       // (the cells of one step have one parity: H[r +- 1] are of step s - 1)
-            const int i = two_i >> 1, j = i + d;
-            int h = kNeg, e = kNeg, f = kNeg;
-            uint32_t bits = 3;
-            if (j >= 0 && j <= n) {
-                const int hl = r > 0 ? H[r > 0 ? r - 1 : 0] : hl_edge, el = r > 0 ? E[r > 0 ? r - 1 : 0] : el_edge;
-                const int hu = r < R - 1 ? H[r < R - 1 ? r + 1 : 0] : hu_edge, fu = r < R - 1 ? F[r < R - 1 ? r + 1 : 0] : fu_edge;
-                const int eo = hl - open_ext, ee = el - ext, fo = hu - open_ext, fe = fu - ext;
-                e = max(eo, ee);
-                f = max(fo, fe);
-                int dg = kNeg;
-                if (j >= 1) {
-                    const int qcd = qc[i - 1], acd = lds[j - 1];
-                    dg = H[r] + ((qcd < 4 && acd < 4) ? (qcd == acd ? match : -mismatch) : 0);
-                }
-                h = max(dg, max(e, f));
-                bits = (dg >= e && dg >= f) ? 0u : (e >= f ? 1u : 2u);
-                bits |= (eo >= ee ? 4u : 0u) | (fo >= fe ? 8u : 0u);
-                h = max(h, kNeg); e = max(e, kNeg); f = max(f, kNeg);
-            }
-            H[r] = h; E[r] = e; F[r] = f;
-            const int k = i - 1;
-            acc[r] |= bits << (4 * (k & 7));
-            if ((k & 7) == 7 || i == m) {
-                tbq[(size_t)(k >> 3) * Bpad + t] = acc[r];
-                acc[r] = 0;
-            }
-        }
-    }
-    // the end cell: the largest H(m, j) of the band, the smallest j (= the smallest t) among equals
-    int best = kNeg, best_t = 0x7fffffff;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int t = lane * R + r;
-        if (t < B && H[r] > best) { best = H[r]; best_t = t; }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const int ob = __shfl_xor(best, sh), ot = __shfl_xor(best_t, sh);
-        if (ob > best || (ob == best && ot < best_t)) { best = ob; best_t = ot; }
-    }
-    if (lane == 0) {
-        const bool none = best < kNoPath;
-        end_out[2 * q] = none ? MP_ANCHOR_NO_SCORE : best;
-        end_out[2 * q + 1] = none ? -1 : best_t;
-    }
-}
-
-// ---- traceback ----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void anchor_trace_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict__ off, int nq,
-                                                           const int32_t *__restrict__ d0v, const uint8_t *__restrict__ acode,
-                                                           const int32_t *__restrict__ col, int n, int W, int R, int permille,
-                                                           const uint32_t *__restrict__ tb, const int64_t *__restrict__ tb_off,
-                                                           const int32_t *__restrict__ end_in, uint8_t *__restrict__ arow, int32_t *__restrict__ meta,
-                                                           uint8_t *__restrict__ ops, const int64_t *__restrict__ ops_off) {
-    const int q = blockIdx.x * 64 + threadIdx.x;
-    if (q >= nq) return;
-    const uint8_t *qb = bytes + off[q];
-    const int m = (int)(off[q + 1] - off[q]), d0 = d0v[q], dlo = d0 - W, B = 2 * W + 1, Bpad = 64 * R;
-    const uint32_t *tbq = tb + tb_off[q];
-    uint8_t *ar = arow + (size_t)q * n;
-    int32_t *mt = meta + (size_t)q * MP_ANCHOR_META;
-    const int score = end_in[2 * q];
-    int t = end_in[2 * q + 1];
-    int n_match = 0, n_ins = 0, n_del = 0, j_first = -1, j_last = -1, status = 0;
-    if (t < 0) status = 3;
-    else {
-        uint8_t *op = ops ? ops + ops_off[q + 1] : nullptr;
-        int i = m, state = 0;
-        bool touch = false;
-        for (;;) {
-            touch = touch || t == 0 || t == B - 1;
-            if (state == 0 && i == 0) break;
-            const int j = i + dlo + t;
-            if (i < 1 || t < 0 || t >= B || j < 0 || j > n) { status |= 4; break; }      // (cannot happen on a path the sweep wrote)
-            const uint32_t nib = (tbq[(size_t)((i - 1) >> 3) * Bpad + t] >> (4 * ((i - 1) & 7))) & 15u;
-            if (state == 0) {
-                const uint32_t src = nib & 3u;
-                if (src == 0) {
-                    if (j < 1) { status |= 4; break; }
-                    const uint8_t ch = qb[i - 1];
-                    ar[j - 1] = upper_letter(ch);
-                    const int cd = base_code(ch);
-                    n_match += cd < 4 && cd == acode[j - 1];
-                    if (j_last < 0) j_last = j - 1;
-                    j_first = j - 1;
-                    if (op) *--op = 'M';
-                    i--;
-                } else if (src == 3) { status |= 4; break; }
-                else state = (int)src;
-            } else if (state == 1) {
-                if (j < 1) { status |= 4; break; }
-                ar[j - 1] = '-';
-                n_del++;
-                if (op) *--op = 'D';
-                if (nib & 4u) state = 0;
-                t--;
-            } else {
-                n_ins++;
-                if (op) *--op = 'I';
-                if (nib & 8u) state = 0;
-                i--;
-                t++;
-            }
-        }
-        if (touch) status |= 2;
-        if ((long long)n_match * 1000 < (long long)permille * m) status |= 1;
-    }
-    mt[0] = score; mt[1] = d0; mt[2] = n_match; mt[3] = n_ins; mt[4] = n_del;
-    mt[5] = j_first >= 0 ? col[j_first] : -1;
-    mt[6] = j_last >= 0 ? col[j_last] : -1;
-    mt[7] = status; mt[8] = j_first; mt[9] = j_last;
-}
 
 // rows [nq][L] as one run of bytes: lane g writes bytes 16 g .. 16 g + 15 (the buffer starts on a hipMalloc boundary)
 __global__ __launch_bounds__(256) void anchor_emit_kernel(const uint8_t *__restrict__ arow, const int32_t *__restrict__ meta,
@@ -346,7 +121,7 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
     for (int64_t &x : c->an_counts) x = 0;
     if (nq == 0) return MP_OK;
     const int n = c->an_n, L = c->an_L, W = c->an_par[4], B = 2 * W + 1;
-    const int R = B <= 64 ? 1 : B <= 128 ? 2 : B <= 256 ? 4 : 8, Bpad = 64 * R;
+    const int R = anchor_lane_diagonals(W), Bpad = 64 * R;
     for (int32_t q = 0; q < nq; q++) {
         const int64_t m = off[q + 1] - off[q];
         if (m < 1 || m > MP_ANCHOR_MAX_LEN) return fail(c, MP_ERR_ARG, "mp_anchor_align: query %d has %lld bases (1..%d)", q, (long long)m, MP_ANCHOR_MAX_LEN);
@@ -434,17 +209,18 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
         if ((e = hipEventRecord(ev[1], c->stream)) != hipSuccess) break;
         const dim3 grid((unsigned)((nb + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
 #define MP_ANCHOR_DP(RR)                                                                                                                         \
-        hipLaunchKernelGGL((anchor_dp_kernel<RR>), grid, block, dp_lds, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off, (int)nb,        \
+        hipLaunchKernelGGL((anchor_dp_kernel<RR, false>), grid, block, dp_lds, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off, (int)nb,        \
                            (const int32_t *)d_d0, (const uint8_t *)c->an_code, n, W, (int)c->an_par[0], (int)c->an_par[1],                          \
-                           (int)(c->an_par[2] + c->an_par[3]), (int)c->an_par[3], mstride, d_tb, (const int64_t *)d_tboff, d_end)
+                           (int)(c->an_par[2] + c->an_par[3]), (int)c->an_par[3], mstride, d_tb, (const int64_t *)d_tboff, d_end,     \
+                           (const int32_t *)nullptr, 0LL)
         if (R == 1) MP_ANCHOR_DP(1); else if (R == 2) MP_ANCHOR_DP(2); else if (R == 4) MP_ANCHOR_DP(4); else MP_ANCHOR_DP(8);
 #undef MP_ANCHOR_DP
         if ((e = hipGetLastError()) != hipSuccess) break;
         if ((e = hipEventRecord(ev[2], c->stream)) != hipSuccess) break;
-        hipLaunchKernelGGL(anchor_trace_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off,
+        hipLaunchKernelGGL((anchor_trace_kernel<false, false>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off,
                            (int)nb, (const int32_t *)d_d0, (const uint8_t *)c->an_code, (const int32_t *)c->an_col, n, W, R, (int)c->an_par[5],
                            (const uint32_t *)d_tb, (const int64_t *)d_tboff, (const int32_t *)d_end, d_arow, d_meta, want_ops ? d_ops : (uint8_t *)nullptr,
-                           (const int64_t *)d_opsoff);
+                           (const int64_t *)d_opsoff, (const int32_t *)nullptr, 0LL, (uint16_t *)nullptr, (uint16_t *)nullptr, 0);
         if ((e = hipGetLastError()) != hipSuccess) break;
         const long long total = (long long)nb * L;
         hipLaunchKernelGGL(anchor_emit_kernel, dim3((unsigned)((total + 4095) / 4096)), dim3(256), 0, c->stream, (const uint8_t *)d_arow,

@@ -301,6 +301,22 @@ struct mp_ctx {
     std::vector<int64_t> cl_off_host;
     double cl_ms[5] = {0, 0, 0, 0, 0};
     int64_t cl_counts[3] = {0, 0, 0};
+    // star alignment (star.hip, include/mprime_star.h): the records of mp_star_load, the last round's path store, columns, rows and counts
+    uint8_t *st_bytes = nullptr;             // [st_total] the records' letters as given, back to back
+    int64_t *st_off = nullptr;               // [st_n + 1]
+    int32_t st_n = 0;
+    size_t st_total = 0;
+    std::vector<int64_t> st_off_host;
+    int32_t st_an = 0, st_stride = 0, st_width = 0;      // of the last round: anchor positions, slots per record of the path store (padded), L'
+    int32_t *st_d0 = nullptr, *st_end = nullptr, *st_meta = nullptr, *st_wfin = nullptr;     // [st_n] / [2 st_n] / [st_n][MP_ANCHOR_META] / [st_n]
+    uint8_t *st_arow = nullptr;              // [st_n][st_an] the aligned letters in anchor space
+    uint16_t *st_runlen = nullptr, *st_qstart = nullptr; // [st_n][st_stride] the path store: inserted run per slot
+    int32_t *st_ins = nullptr, *st_acol = nullptr;       // [st_stride] each (st_an + 1 used)
+    int32_t *st_colmap = nullptr;            // [st_width] anchor position of a column, or ~slot
+    uint8_t *st_rows = nullptr;              // [st_n][st_width]
+    int32_t *st_colcnt = nullptr;            // [st_width][6]
+    double st_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t st_counts[6] = {0, 0, 0, 0, 0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run
@@ -411,6 +427,7 @@ void free_unique(mp_ctx *c);
 void free_seq(mp_ctx *c);        // scan.hip
 void free_anchor(mp_ctx *c);     // anchor.hip
 void free_cluster(mp_ctx *c);    // cluster.hip
+void free_star(mp_ctx *c);       // star.hip
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

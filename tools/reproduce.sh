@@ -196,5 +196,11 @@ cluster)         # profiles/cluster_scale.txt: clustering by identity, 10^4 .. 1
   timeout -k 10 300 python -m pytest tests/test_cluster_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
   timeout -k 10 1100 python tools/cluster_bench.py --out $O/cluster_scale.txt &&
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_cluster -- python tools/cluster_bench.py --records 100000 --repeats 0 2>&1 | tail -5 ;;
+star)            # profiles/star_msa.txt and profiles/star_scale.txt: the star alignment on the workflow's own cluster (agreement with mafft per number of rounds) and on 10^4 .. 10^6 records of 1 kb, two rounds at W = 32; then the kernel trace in a run of its own
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 600 python -m pytest tests/test_star_gpu.py -x -q -s -m gpu 2>&1 | tee $O/star_msa.txt | tail -4 &&
+  timeout -k 10 1100 python tools/star_bench.py --out $O/star_scale.txt &&
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_star -- python tools/star_bench.py --no-cluster --records 1000000 --repeats 0 2>&1 | tail -5 ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
