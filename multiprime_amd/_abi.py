@@ -676,10 +676,13 @@ class Context:
 
     # (8b) the resident sequence store
     def seq_load(self, data, row_off):
-        """The unaligned database of the PCR / k-mismatch scans, uploaded and packed once (mp_seq_load); the *_resident scans use it."""
+        """The unaligned database of the PCR / k-mismatch scans, uploaded and packed once (mp_seq_load); the *_resident scans use it.
+        Records may all be empty: the library refuses a null text with n_rows > 0, so a text of no bytes still goes as a valid pointer."""
         data = np.ascontiguousarray(data, dtype=np.uint8)
         row_off = np.ascontiguousarray(row_off, dtype=np.int64)
-        self._ck(self.d.mp_seq_load(self.h, _ptr(data) if len(data) else None, _ptr(row_off), len(row_off) - 1))
+        if not len(data):
+            data = np.zeros(1, np.uint8)
+        self._ck(self.d.mp_seq_load(self.h, _ptr(data), _ptr(row_off), len(row_off) - 1))
 
     def seq_free(self):
         self._ck(self.d.mp_seq_free(self.h))

@@ -1007,20 +1007,25 @@ int mp_pair_coverage(mp_ctx *c, int32_t n_sets, int32_t n_words, const uint64_t 
     unsigned long long *d_a = nullptr, *d_b = nullptr;
     int32_t *d_pairs = nullptr, *d_out = nullptr;
     int rc;
-    if ((rc = dev_alloc(c, &d_a, nset))) return rc;
-    if ((rc = dev_alloc(c, &d_b, nset))) return rc;
-    if ((rc = dev_alloc(c, &d_pairs, (size_t)2 * n_pairs))) return rc;
-    if ((rc = dev_alloc(c, &d_out, (size_t)n_pairs))) return rc;
-    HIPCK(c, hipMemcpyAsync(d_a, a, sizeof(uint64_t) * nset, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d_b, b, sizeof(uint64_t) * nset, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    const long long per_block = kBlock / 64;
-    hipLaunchKernelGGL(pair_coverage_kernel, dim3((unsigned)((n_pairs + per_block - 1) / per_block)), dim3(kBlock), 0, c->stream,
-                       d_a, d_b, n_words, (long long)n_pairs, d_pairs, d_out);
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipMemcpyAsync(out, d_out, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    dev_free(c, &d_a, nset); dev_free(c, &d_b, nset); dev_free(c, &d_pairs, (size_t)2 * n_pairs); dev_free(c, &d_out, (size_t)n_pairs);
+    auto cleanup = [&]() {
+        dev_free(c, &d_a, nset); dev_free(c, &d_b, nset); dev_free(c, &d_pairs, (size_t)2 * n_pairs); dev_free(c, &d_out, (size_t)n_pairs);
+    };
+    if ((rc = dev_alloc(c, &d_a, nset)) || (rc = dev_alloc(c, &d_b, nset)) || (rc = dev_alloc(c, &d_pairs, (size_t)2 * n_pairs)) ||
+        (rc = dev_alloc(c, &d_out, (size_t)n_pairs))) { cleanup(); return rc; }
+    hipError_t e = hipMemcpyAsync(d_a, a, sizeof(uint64_t) * nset, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_b, b, sizeof(uint64_t) * nset, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        const long long per_block = kBlock / 64;
+        hipLaunchKernelGGL(pair_coverage_kernel, dim3((unsigned)((n_pairs + per_block - 1) / per_block)), dim3(kBlock), 0, c->stream,
+                           d_a, d_b, n_words, (long long)n_pairs, d_pairs, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    else (void)hipStreamSynchronize(c->stream);        // the copies above read host memory of the caller: none may be in flight on return
+    cleanup();
+    if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "mp_pair_coverage: %s", hipGetErrorString(e));
     return MP_OK;
 }
 

@@ -81,6 +81,12 @@ def test_resident_scans_equal_the_byte_scans_and_the_oracle(hip_lib, oracle_lib,
     try:
         h.seq_load(data, off)
         assert np.array_equal(h.pcr_scan_resident(codes, poff), o.pcr_scan(data, off, codes, poff))
+        # the k-mismatch scan of the store against the checker's byte scan (the patterns and settings of _check)
+        pat = [np.frombuffer(s.upper(), np.uint8) for s in seqs if len(s) >= 200][:3]
+        pc = np.concatenate([iupac.MASK_LUT[np.where(np.isin(p[40:40 + length], [65, 67, 71, 84]), p[40:40 + length], 65)] for p in pat]).astype(np.uint8)
+        po = np.arange(len(pat) + 1, dtype=np.int32) * length
+        for mm, term in ((0, 0), (2, 3), (3, 0)):
+            assert np.array_equal(h.kmm_scan_resident(pc, po, mm, term), o.kmm_scan(data, off, pc, po, mm, term))
         # a second load replaces the store
         h.seq_load(data[: off[5]], off[:6])
         assert np.array_equal(h.pcr_scan_resident(codes, poff), o.pcr_scan(data[: off[5]], off[:6], codes, poff))
