@@ -155,8 +155,11 @@ struct DevEnv {
         for (int i = 0; i < GW; i++) z[i] = 0u;
         for (int s = 0; s < k; s++) ring_put(ring + s * (64 * GW), z);
     }
-    __device__ __forceinline__ void ring_write(int slot, const uint32_t (&in)[GW]) { ring_put(ring + slot * (64 * GW), in); }
-    __device__ __forceinline__ void ring_read(int slot, uint32_t (&o)[GW]) const { ring_get(ring + slot * (64 * GW), o); }
+    // a slot is named by its wave-uniform byte offset from slot 0 (slidecore.hpp keeps and advances the offsets): one add of the lane's base
+    __device__ __forceinline__ uint32_t ring_step() const { return 64u * GW * (uint32_t)sizeof(uint32_t); }
+    __device__ __forceinline__ uint32_t *ring_at(uint32_t off) const { return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ring) + off); }
+    __device__ __forceinline__ void ring_write(uint32_t off, const uint32_t (&in)[GW]) { ring_put(ring_at(off), in); }
+    __device__ __forceinline__ void ring_read(uint32_t off, uint32_t (&o)[GW]) const { ring_get(ring_at(off), o); }
     // The wave's OUT counts of the item's 8 member slots into the workgroup's table: 12 words per item, two 16-bit counts each
     // (registers 0-7: out1 | outF << 16 of slot q; 8-11: outR of slots 2 (q - 8), 2 (q - 8) + 1) — a workgroup covers 4 x 64 x 32 GW
     // <= 32768 rows, so a field never carries.
@@ -418,7 +421,8 @@ int launch_eval_slide(mp_ctx *c, unsigned long long *device_out, const EvalChain
     const int nw32 = c->n_pad / 32;
     SlideKernArgs K;
     K.A = SlideArgs{c->slide_bands, c->slide_iters, c->slide_recs, c->k, c->p0, c->slide_ns, c->slide_spos, c->slide_fmask, c->slide_rmask,
-                    (uint32_t)nw32 * 4u, c->slide_fpos, c->slide_rpos};
+                    (uint32_t)nw32 * 4u, c->slide_fpos, c->slide_rpos, 0u, 0u};
+    if (c->slide_fast) slide_strict_distinct(c->slide_fpos, c->slide_rpos, K.A.dpos, K.A.dshape);
     K.cols32 = reinterpret_cast<const uint32_t *>(c->cols);
     K.excl32 = reinterpret_cast<const uint32_t *>(c->excl);
     K.nw32 = nw32;

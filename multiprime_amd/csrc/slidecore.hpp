@@ -98,6 +98,7 @@ struct SlideArgs {
     uint32_t spos, fmask, rmask;
     uint32_t row_scale;                // plane row -> what Env::fetch takes (bytes of a plane row on the GPU, 1 in the emulation)
     uint32_t fpos, rpos;               // FAST strict form (slide_strict_lists): up to three forward / reverse strict positions, 5 bits each, their number << 15
+    uint32_t dpos, dshape;             // FAST: the DISTINCT strict positions of both sides and how many are whose (slide_strict_distinct)
 };
 
 // The strict positions of a launch as two lists (forward, reverse) of at most three positions each — what `-c` gives by default (V20:85:
@@ -112,6 +113,31 @@ inline bool slide_strict_lists(int k, uint32_t sF, uint32_t sR, uint32_t &fpos, 
     fpos |= nf << 15; rpos |= nr << 15;
     return true;
 }
+
+// The distinct strict positions of the two lists, 5 bits each in dpos, in the order [on both sides, forward only, reverse only]; dshape =
+// their numbers nB | nFo << 2 | nRo << 4.  A side's sum is symmetric in its positions, so the three numbers are all the band routine has to
+// know to read every distinct position once: forward = the first nB + nFo entries, reverse = the first nB and the last nRo.
+inline void slide_strict_distinct(uint32_t fpos, uint32_t rpos, uint32_t &dpos, uint32_t &dshape) {
+    const int nf = (int)(fpos >> 15), nr = (int)(rpos >> 15);
+    uint32_t fm = 0, rm = 0;
+    for (int q = 0; q < nf; q++) fm |= 1u << ((fpos >> (5 * q)) & 31u);
+    for (int q = 0; q < nr; q++) rm |= 1u << ((rpos >> (5 * q)) & 31u);
+    const uint32_t sets[3] = {fm & rm, fm & ~rm, rm & ~fm};
+    int n = 0, cnt[3] = {0, 0, 0};
+    dpos = 0u;
+    for (int c = 0; c < 3; c++)
+        for (int j = 0; j < 32; j++)
+            if ((sets[c] >> j) & 1u) { dpos |= (uint32_t)j << (5 * n++); cnt[c]++; }
+    dshape = (uint32_t)cnt[0] | ((uint32_t)cnt[1] << 2) | ((uint32_t)cnt[2] << 4);
+}
+constexpr uint32_t slide_shape_code(int nb, int nfo, int nro) { return (uint32_t)nb | ((uint32_t)nfo << 2) | ((uint32_t)nro << 4); }
+constexpr uint32_t kSlShapeDefault = slide_shape_code(1, 1, 2);      // `-c 2,3,-1`: {2, 3} forward, {2, k - 3, k - 2} reverse — one shared, one and two of their own
+
+// How a band reads its strict positions (FAST), fixed at compile time so that the window loop holds no launch constant: the numbers of
+// slide_strict_distinct — every distinct position read once, nothing zero-filled — or MASKED: one read per side and list entry (NFO = NRO = 3),
+// an entry the launch does not have read anyway and met by an empty mask (any lists; two more instructions per word and absent entry).
+template <int NB_, int NFO_, int NRO_, bool MASKED_>
+struct SlideShape { static constexpr int NB = NB_, NFO = NFO_, NRO = NRO_, ND = NB_ + NFO_ + NRO_; static constexpr bool MASKED = MASKED_; };
 
 // The planes an item needs beyond the sliding count: its event planes (entries 1 .. n_slots - 1) and the rows its window lets the
 // column-plane pass count.  Requested one item AHEAD of their use (slide_band), so that an item's memory latency hides behind the
@@ -341,7 +367,7 @@ SLIDE_HD void slide_item(Env &env, const SlideArgs &A, const typename Env::Rec &
 // third of the kernel's time at the 131072-row shard, where every wave of the chip warms up at the same moment
 // (tools/r05_exp2.sh: 17 columns, ~10 us of 29).
 template <int N, int GW, class Env>
-SLIDE_HD void slide_warm_chunk(Env &env, SlideCount (&cnt)[GW], int &slot, int j) {
+SLIDE_HD void slide_warm_chunk(Env &env, SlideCount (&cnt)[GW], uint32_t &cur, int j) {
     uint32_t w[N][GW];
 #pragma unroll
     for (int u = 0; u < N; u++) env.fetch(env.iter_word(2 * (j + u)), w[u]);
@@ -353,8 +379,8 @@ SLIDE_HD void slide_warm_chunk(Env &env, SlideCount (&cnt)[GW], int &slot, int j
             bn[i] = ~w[u][i];                                           // rows that do not carry the reference base here
             slide_updown(cnt[i], bn[i], bn[i]);                         // all of them go up
         }
-        env.ring_write(slot, bn);
-        slot++;                                                         // (warm-up columns never wrap: fewer than k of them)
+        env.ring_write(cur, bn);
+        cur += env.ring_step();                                         // (warm-up columns never wrap: fewer than k of them)
     }
 }
 
@@ -364,7 +390,10 @@ SLIDE_HD void slide_warm_chunk(Env &env, SlideCount (&cnt)[GW], int &slot, int j
 //   fetch(plane_row x row_scale, d)    the lane's words of column plane row `plane_row` (= column * 4 + base)
 //   fetch_event(...)                   the same for an item's event planes (one function in every product build)
 //   valid_of(window x row_scale, v)    rows the column-plane pass may count for this window
-//   ring_zero(k); ring_write(slot, in); ring_read(slot, out)
+//   ring_zero(k); ring_step() = the distance of two ring slots in what ring_write / ring_read take (bytes of LDS on the GPU, words in the
+//   emulation); ring_write(off, in); ring_read(off, out) with off = slot x ring_step(), wave-uniform.  The band routine never multiplies:
+//   it keeps the offset of the slot it writes and one per strict position it reads, and moves each on by one slot per window (add, compare,
+//   select) — the environment only adds the lane's base.
 //   progress(quarter)                  quarters of the band behind the wave (a hint for the issue priority)
 //   commit(item_in_band, accPF, accR)  the lane's OUT counts of the item's 8 member slots (layout: slide_item)
 // Software pipeline: the column sliding in is requested two iterations ahead, an item's record two items ahead, its planes one item
@@ -386,7 +415,8 @@ SLIDE_HD void slide_band(Env &env, const SlideArgs &A, int band_index) {
 #pragma unroll
     for (int i = 0; i < GW; i++) cnt[i] = SlideCount{0u, 0u, 0u, 0u, 0u};
     env.ring_zero(k);                                                   // a slot's first visitor slides nothing out
-    int slot = 0;
+    const uint32_t ring_step = env.ring_step(), ring_end = (uint32_t)k * ring_step;
+    uint32_t cur = 0u;                                                  // offset of the slot the next column is written to
     const int n_iter = bd.n_win + k - 1;                                // k - 1 warm-up columns, then one column per window
     const int last_item = bd.item0 + bd.n_items - 1;
     // item pipeline: records of the next two items, planes of the next one (set 0 first)
@@ -402,10 +432,10 @@ SLIDE_HD void slide_band(Env &env, const SlideArgs &A, int band_index) {
     int j0 = 0;
     {
         const int n_warm = k - 1 < n_iter ? k - 1 : n_iter;
-        while (n_warm - j0 >= 16) { slide_warm_chunk<16, GW>(env, cnt, slot, j0); j0 += 16; }
-        if (n_warm - j0 >= 8) { slide_warm_chunk<8, GW>(env, cnt, slot, j0); j0 += 8; }
-        if (n_warm - j0 >= 4) { slide_warm_chunk<4, GW>(env, cnt, slot, j0); j0 += 4; }
-        if (n_warm - j0 >= 2) { slide_warm_chunk<2, GW>(env, cnt, slot, j0); j0 += 2; }
+        while (n_warm - j0 >= 16) { slide_warm_chunk<16, GW>(env, cnt, cur, j0); j0 += 16; }
+        if (n_warm - j0 >= 8) { slide_warm_chunk<8, GW>(env, cnt, cur, j0); j0 += 8; }
+        if (n_warm - j0 >= 4) { slide_warm_chunk<4, GW>(env, cnt, cur, j0); j0 += 4; }
+        if (n_warm - j0 >= 2) { slide_warm_chunk<2, GW>(env, cnt, cur, j0); j0 += 2; }
     }
     env.stamp(3);
     // column pipeline: iteration j's column waits in set j & 1
@@ -426,75 +456,6 @@ SLIDE_HD void slide_band(Env &env, const SlideArgs &A, int band_index) {
         env.commit(done, accPF, accR);
         done++;
     };
-    // one iteration: the column waiting in `b` slides in (the column it pushes out of the ring was read an iteration ago into `bo`),
-    // `b` is refilled with the column two iterations on, `bo` with the next iteration's outgoing column, the window's items run
-    auto iteration = [&](uint32_t (&b)[GW], uint32_t (&bo)[GW], uint32_t (&bo_next)[GW], int j) __attribute__((always_inline)) {
-        const uint32_t it1 = env.iter_word(2 * j + 1);
-        uint32_t bn[GW];
-#pragma unroll
-        for (int i = 0; i < GW; i++) bn[i] = ~b[i];                    // rows that do not carry the reference base here
-        env.fetch(env.iter_word(2 * j + 4), b);                        // (past the band's end: a row of the next band, unused)
-#pragma unroll
-        for (int i = 0; i < GW; i++) slide_updown(cnt[i], bn[i] ^ bo[i], bn[i]);
-        env.ring_write(slot, bn);                                      // the column sliding out shared the slot (k columns apart)
-        const int slot_now = slot;
-        slot = slot + 1 == k ? 0 : slot + 1;
-        env.ring_read(slot, bo_next);
-        const int n_items = (int)(it1 >> 24);
-        if (n_items == 0) return;                                      // warming up, or a window without chains
-        // mismatch words of the reference at the strict positions of this window, out of the ring (slots beyond the launch's strict
-        // positions read position 0 and meet empty masks)
-        uint32_t sv[kSlideStrict][GW];
-        if (FAST) {
-            // the reference's mismatch words at the side's (up to three) strict positions, summed: bit 0 = xor3, bit 1 = majority
-            uint32_t p[2][3][GW];
-#pragma unroll
-            for (int side = 0; side < 2; side++) {
-                const uint32_t pos = side ? A.rpos : A.fpos;
-                const int n = (int)(pos >> 15);
-#pragma unroll
-                for (int q = 0; q < 3; q++) {
-                    if (SLIDE_UNLIKELY(q >= n)) {
-#pragma unroll
-                        for (int i = 0; i < GW; i++) p[side][q][i] = 0u;
-                    } else {
-                        int s = slot_now + 1 + (int)((pos >> (5 * q)) & 31u);
-                        if (s >= k) s -= k;
-                        env.ring_read(s, p[side][q]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int side = 0; side < 2; side++)
-#pragma unroll
-                for (int i = 0; i < GW; i++) {
-                    sv[2 * side][i] = bop<kSlXor3>(p[side][0][i], p[side][1][i], p[side][2][i]);
-                    sv[2 * side + 1][i] = bop<kSlMaj>(p[side][0][i], p[side][1][i], p[side][2][i]);
-                }
-        }
-#pragma unroll
-        for (int q = 0; q < kSlideStrict; q++) {
-            if (FAST) break;
-            if (q < 4 || A.ns > 4) {
-                int s = slot_now + 1 + (int)((A.spos >> (5 * q)) & 31u);
-                if (s >= k) s -= k;
-                env.ring_read(s, sv[q]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < GW; i++) sv[q][i] = 0u;
-            }
-        }
-        // items in pairs: inside the loop the two register sets have fixed roles (a loop over single items that picks the set by parity
-        // ends in one copy of the code that moves the freshly loaded set into place: 14 moves and a wait for the youngest load per item)
-        int ii = 0;
-        if (done & 1) { item(rec1, rec0, F1, F0, sv); ii = 1; }
-#pragma unroll 1
-        for (; ii + 1 < n_items; ii += 2) {
-            item(rec0, rec1, F0, F1, sv);
-            item(rec1, rec0, F1, F0, sv);
-        }
-        if (ii < n_items) item(rec0, rec1, F0, F1, sv);
-    };
     // quarters of the band's windows behind the wave (the warm-up columns are nobody's progress: every wave has them).  Long bands only:
     // with the 8-window bands of a 131072-row shard the workgroups of a CU ending together only delays the patch units that wait for
     // their slots (tools/r05_prio.sh, profiles/r05_exp_prio.txt: 0.0334 against 0.0312 ms)
@@ -502,22 +463,133 @@ SLIDE_HD void slide_band(Env &env, const SlideArgs &A, int band_index) {
 #define SLIDE_PRIO_MIN_WIN 32
 #endif
     const int quarter_len = bd.n_win < SLIDE_PRIO_MIN_WIN ? 1 << 20 : ((bd.n_win + 3) / 4 > 2 ? (bd.n_win + 3) / 4 : 2);
-    int quarter = 0, next_quarter = k - 1 + quarter_len;
-    env.progress(0);
-    uint32_t boA[GW], boB[GW];
-    env.ring_read(slot, boA);                                           // zeros: the first k columns push nothing out
-#pragma unroll 1
-    for (int base = 0; base < n_iter; base += 30) {                     // 64 iteration words = 32 iterations, two of them look-ahead
-        if (base) env.load_iters(bd.iter0 + 2 * base);
-        const int n_here = n_iter - base < 30 ? n_iter - base : 30;     // 30 is even: an iteration's parity is that of j
-        int j = base ? 0 : j0;                                          // (j0 is even and at most 30)
-#pragma unroll 1
-        for (; j + 1 < n_here; j += 2) {
-            if (base + j >= next_quarter) { env.progress(++quarter); next_quarter += quarter_len; }
-            iteration(bA, boA, boB, j);
-            iteration(bB, boB, boA, j + 1);
+    // The window loop, once per way of reading the strict positions (SlideShape; the per-position form !FAST reads its kSlideStrict slots).
+    auto run = [&](auto shape) __attribute__((always_inline)) {
+        typedef decltype(shape) Shape;
+        constexpr int NS = Shape::ND;                                    // ring offsets that follow the window (!FAST: the launch's strict slots, 4 or 6)
+        // Offset of strict entry q in the window BEHIND iteration j0's: position p of the window whose newest column sits in slot s is in
+        // slot (s + 1 + p) mod k, and iteration j0 writes slot j0.  Once per band; from here on every offset moves one slot per window.
+        uint32_t so[NS > 0 ? NS : 1], sm[NS > 0 ? NS : 1];
+#pragma unroll
+        for (int q = 0; q < NS; q++) {
+            uint32_t pos, present = 1u;
+            if (!FAST) pos = (A.spos >> (5 * q)) & 31u;                  // (slots beyond the launch's strict positions: position 0, empty masks)
+            else if (!Shape::MASKED) pos = (A.dpos >> (5 * q)) & 31u;
+            else {
+                const uint32_t list = q < 3 ? A.fpos : A.rpos;
+                const int qq = q < 3 ? q : q - 3;
+                present = qq < (int)(list >> 15) ? 1u : 0u;
+                pos = present ? (list >> (5 * qq)) & 31u : 0u;
+            }
+            so[q] = (((uint32_t)j0 + pos) % (uint32_t)k) * ring_step;
+            sm[q] = present ? 0xFFFFFFFFu : 0u;
         }
-        if (j < n_here) iteration(bA, boA, boB, j);                     // (an odd tail ends the band)
+        // one iteration: the column waiting in `b` slides in (the column it pushes out of the ring was read an iteration ago into `bo`),
+        // `b` is refilled with the column two iterations on, `bo` with the next iteration's outgoing column, the window's items run
+        auto iteration = [&](uint32_t (&b)[GW], uint32_t (&bo)[GW], uint32_t (&bo_next)[GW], int j) __attribute__((always_inline)) {
+            const uint32_t it1 = env.iter_word(2 * j + 1);
+            uint32_t bn[GW];
+#pragma unroll
+            for (int i = 0; i < GW; i++) bn[i] = ~b[i];                // rows that do not carry the reference base here
+            env.fetch(env.iter_word(2 * j + 4), b);                    // (past the band's end: a row of the next band, unused)
+#pragma unroll
+            for (int i = 0; i < GW; i++) slide_updown(cnt[i], bn[i] ^ bo[i], bn[i]);
+            env.ring_write(cur, bn);                                   // the column sliding out shared the slot (k columns apart)
+            cur += ring_step;
+            if (cur == ring_end) cur = 0u;
+            env.ring_read(cur, bo_next);
+#pragma unroll
+            for (int q = 0; q < NS; q++) {                             // (a window without chains moves them on too)
+                so[q] += ring_step;
+                if (so[q] == ring_end) so[q] = 0u;
+            }
+            const int n_items = (int)(it1 >> 24);
+            if (n_items == 0) return;                                  // warming up, or a window without chains
+            // mismatch words of the reference at the strict positions of this window, out of the ring
+            uint32_t sv[kSlideStrict][GW];
+            if (FAST) {
+                // the reference's mismatch words at the side's (up to three) strict positions, summed: bit 0 = xor3, bit 1 = majority
+                uint32_t d[NS > 0 ? NS : 1][GW];
+#pragma unroll
+                for (int q = 0; q < NS; q++) {
+                    env.ring_read(so[q], d[q]);
+                    if (Shape::MASKED) {
+#pragma unroll
+                        for (int i = 0; i < GW; i++) d[q][i] &= sm[q];
+                    }
+                }
+                constexpr int NF = Shape::NB + Shape::NFO, NR = Shape::NB + Shape::NRO;
+                static_assert(NF <= 3 && NR <= 3, "at most three strict positions per side");
+#pragma unroll
+                for (int i = 0; i < GW; i++) {
+                    uint32_t f[3] = {0u, 0u, 0u}, r[3] = {0u, 0u, 0u};
+#pragma unroll
+                    for (int q = 0; q < NF; q++) f[q] = d[q][i];
+#pragma unroll
+                    for (int q = 0; q < NR; q++) r[q] = d[q < Shape::NB ? q : q + Shape::NFO][i];
+                    sv[0][i] = NF == 3 ? bop<kSlXor3>(f[0], f[1], f[2]) : (f[0] ^ f[1]);
+                    sv[1][i] = NF == 3 ? bop<kSlMaj>(f[0], f[1], f[2]) : (f[0] & f[1]);
+                    sv[2][i] = NR == 3 ? bop<kSlXor3>(r[0], r[1], r[2]) : (r[0] ^ r[1]);
+                    sv[3][i] = NR == 3 ? bop<kSlMaj>(r[0], r[1], r[2]) : (r[0] & r[1]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < kSlideStrict; q++) {
+                if (FAST) break;
+                if (q < NS) {
+                    env.ring_read(so[q], sv[q]);
+                } else {                                               // (a launch with at most four strict positions: slide_item never looks)
+#pragma unroll
+                    for (int i = 0; i < GW; i++) sv[q][i] = 0u;
+                }
+            }
+            // items in pairs: inside the loop the two register sets have fixed roles (a loop over single items that picks the set by parity
+            // ends in one copy of the code that moves the freshly loaded set into place: 14 moves and a wait for the youngest load per item)
+            int ii = 0;
+            if (done & 1) { item(rec1, rec0, F1, F0, sv); ii = 1; }
+#pragma unroll 1
+            for (; ii + 1 < n_items; ii += 2) {
+                item(rec0, rec1, F0, F1, sv);
+                item(rec1, rec0, F1, F0, sv);
+            }
+            if (ii < n_items) item(rec0, rec1, F0, F1, sv);
+        };
+        int quarter = 0, next_quarter = k - 1 + quarter_len;
+        env.progress(0);
+        uint32_t boA[GW], boB[GW];
+        env.ring_read(cur, boA);                                        // zeros: the first k columns push nothing out
+#pragma unroll 1
+        for (int base = 0; base < n_iter; base += 30) {                 // 64 iteration words = 32 iterations, two of them look-ahead
+            if (base) env.load_iters(bd.iter0 + 2 * base);
+            const int n_here = n_iter - base < 30 ? n_iter - base : 30; // 30 is even: an iteration's parity is that of j
+            int j = base ? 0 : j0;                                      // (j0 is even and at most 30)
+#pragma unroll 1
+            for (; j + 1 < n_here; j += 2) {
+                if (base + j >= next_quarter) { env.progress(++quarter); next_quarter += quarter_len; }
+                iteration(bA, boA, boB, j);
+                iteration(bB, boB, boA, j + 1);
+            }
+            if (j < n_here) iteration(bA, boA, boB, j);                 // (an odd tail ends the band)
+        }
+    };
+    // Which way is a launch constant, decided here — outside the window loop — and not a kernel parameter.  The shapes that `-c` gives when
+    // nothing coincides (n positions on either side, none shared: n = 0 .. 3), its default (kSlShapeDefault) and one position that is
+    // strict on both sides read their distinct positions once and nothing else — no absent entry, no mask.  Every other pair of lists
+    // (positions that happen to coincide, a side that lost a position beyond the window) takes the masked form.  One more copy of the
+    // window loop per shape: the whole table would be thirty.
+    if constexpr (!FAST) {
+        if (A.ns > 4) run(SlideShape<0, 3, 3, false>());                // ND = 6 strict slots
+        else run(SlideShape<0, 2, 2, false>());                         // ND = 4
+    } else {
+        switch (A.dshape) {
+            case kSlShapeDefault: run(SlideShape<1, 1, 2, false>()); break;
+            case slide_shape_code(0, 0, 0): run(SlideShape<0, 0, 0, false>()); break;
+            case slide_shape_code(1, 0, 0): run(SlideShape<1, 0, 0, false>()); break;
+            case slide_shape_code(0, 1, 1): run(SlideShape<0, 1, 1, false>()); break;
+            case slide_shape_code(0, 2, 2): run(SlideShape<0, 2, 2, false>()); break;
+            case slide_shape_code(0, 3, 3): run(SlideShape<0, 3, 3, false>()); break;
+            default: run(SlideShape<0, 3, 3, true>()); break;
+        }
     }
     env.progress(3);
 }

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 
 #include "../multiprime_amd/csrc/slidecore.hpp"
 
@@ -51,11 +52,13 @@ struct HostEnv {
     void stamp(int) const {}
     void progress(int) const {}
     void ring_zero(int k) { for (int i = 0; i < k * GW; i++) ring[(size_t)i] = 0u; }
-    void ring_write(int slot, const uint32_t (&in)[GW]) {
-        for (int i = 0; i < GW; i++) ring[(size_t)slot * GW + i] = in[i];
+    // a slot is named by its offset in words (the GPU: in bytes of LDS); the band routine advances the offsets itself
+    uint32_t ring_step() const { return (uint32_t)GW; }
+    void ring_write(uint32_t off, const uint32_t (&in)[GW]) {
+        for (int i = 0; i < GW; i++) ring.at((size_t)off + i) = in[i];
     }
-    void ring_read(int slot, uint32_t (&o)[GW]) const {
-        for (int i = 0; i < GW; i++) o[i] = ring[(size_t)slot * GW + i];
+    void ring_read(uint32_t off, uint32_t (&o)[GW]) const {
+        for (int i = 0; i < GW; i++) o[i] = ring.at((size_t)off + i);
     }
     void commit(int done, const uint32_t (&accPF)[8], const uint32_t (&accR)[4]) {
         const int item = band.item0 + done;
@@ -72,15 +75,20 @@ struct HostEnv {
     }
 };
 
-static void make_case(Case &C, std::mt19937 &rng, int trial) {
+// `ring` mode (main): the shape is given, only the alignment and the chains are random
+struct Fixed { int k, v, rows, band; uint32_t sF, sR; };
+
+static void make_case(Case &C, std::mt19937 &rng, int trial, const Fixed *fx = nullptr) {
     auto U = [&](int n) { return (int)(rng() % (unsigned)n); };
     C.k = 2 + U(30);
     if (trial % 3 == 0) C.k = 18;
     C.v = U(4);
     C.n_rows = 40 + U(900);
+    if (fx) { C.k = fx->k; C.v = fx->v; C.n_rows = fx->rows; }
     C.nw32 = (C.n_rows + 31) / 32;
     C.n_cols = C.k + 20 + U(120);
     C.p0 = U(5);
+    if (fx && C.n_cols < C.p0 + C.k + fx->band + 12) C.n_cols = C.p0 + C.k + fx->band + 12;      // ring mode: a whole band of the asked length and a shorter one behind it
     C.W = C.n_cols - C.p0 - C.k + 1 - U(3);
     if (C.W < 1) C.W = 1;
     std::vector<uint8_t> root((size_t)C.n_cols);
@@ -109,12 +117,13 @@ static void make_case(Case &C, std::mt19937 &rng, int trial) {
     const int n_strict = U(5);
     for (int i = 0; i < n_strict; i++) { const int j = U(C.k); if (U(2)) C.sF |= 1u << j; if (U(2)) C.sR |= 1u << j; }
     if (trial % 3 == 0) { C.sF = (1u << 2) | (1u << 3); C.sR = (1u << 2) | (1u << (C.k - 3)) | (1u << (C.k - 2)); }
+    if (fx) { C.sF = fx->sF; C.sR = fx->sR; }
     C.sF &= kmask; C.sR &= kmask;
     C.chains.clear(); C.events.clear(); C.cand_out.clear(); C.members.clear(); C.cand_win.clear();
     const int skip_pct = U(40);
     for (int w = 0; w < C.W; w++) {
-        if (U(100) < skip_pct) continue;
-        if (U(25) == 0) { w += C.k + U(6); if (w >= C.W) break; }                   // a gap: the next band warms up afresh
+        if (fx ? w % 7 == 3 : U(100) < skip_pct) continue;                           // (ring mode: windows without chains INSIDE the bands, no gaps)
+        if (!fx && U(25) == 0) { w += C.k + U(6); if (w >= C.W) break; }            // a gap: the next band warms up afresh
         const int n_chains = 1 + (U(5) == 0);
         for (int ci = 0; ci < n_chains; ci++) {
             const int n = 1 + U(8);
@@ -123,7 +132,7 @@ static void make_case(Case &C, std::mt19937 &rng, int trial) {
             for (int j = 0; j < C.k; j++) {
                 uint8_t s = (uint8_t)(1u << root[(size_t)(C.p0 + w + j)]);
                 if (trial % 2 && U(12) == 0) s = (uint8_t)(1u << U(4));               // a seed that is not the consensus
-                if (U(20) == 0) s |= (uint8_t)(1u << U(4));
+                if (U(20) == 0 && !fx) s |= (uint8_t)(1u << U(4));                    // (ring mode: seeds on the consensus, so that the items slide)
                 mem[(size_t)n - 1][(size_t)j] = s;
             }
             int budget = 7;
@@ -179,8 +188,9 @@ static void brute(const Case &C, std::vector<long long> &out) {
 template <int LV, int GW>
 static void run_plan(const Case &C, const SlidePlan &P, std::vector<long long> &out, bool only_simple, bool use_valid, bool fast) {
     out.assign(C.members.size() * 3, 0);
-    SlideArgs A{P.bands.data(), P.iters.data(), P.recs.data(), P.k, C.p0, P.ns, P.spos, P.fmask, P.rmask, 1u, 0u, 0u};
+    SlideArgs A{P.bands.data(), P.iters.data(), P.recs.data(), P.k, C.p0, P.ns, P.spos, P.fmask, P.rmask, 1u, 0u, 0u, 0u, 0u};
     if (fast && (!only_simple || !slide_strict_lists(C.k, C.sF, C.sR, A.fpos, A.rpos))) { fprintf(stderr, "fast form asked for a plan it does not serve\n"); exit(3); }
+    if (fast) slide_strict_distinct(A.fpos, A.rpos, A.dpos, A.dshape);
     for (size_t b = 0; b < P.bands.size(); b++)
         for (int w0 = 0; w0 < C.nw32; w0 += GW) {
             HostEnv<GW> env(C, P, w0, out);
@@ -192,61 +202,94 @@ static void run_plan(const Case &C, const SlidePlan &P, std::vector<long long> &
         }
 }
 
+// One case against brute force in the per-position form and, where the strict sets allow it, the two-bit form.  0 = equal.
+struct Tally { int slid = 0, refused = 0, n_fast = 0; long long items_slid = 0, items_rest = 0; };
+static int check_case(Case &C, int B, bool only_simple, bool use_valid, int gw, int trial, bool with_slow, Tally &T) {
+    SlidePlan P;
+    if (!use_valid)
+        for (auto &w : C.valid) w = 0xFFFFFFFFu;                       // (rows past n_rows are all gaps: they never reach a count)
+    if (!build_slide_plan(C.chains, C.events, C.cand_out, C.k, C.sF, C.sR, C.p0, C.n_cols, B, 1u, only_simple, P)) { T.refused++; return 0; }
+    P.iters.resize(P.iters.size() + 64, 0u);                          // as upload_eval_slide pads it
+    T.slid++;
+    std::vector<long long> want, got, got_fast;
+    brute(C, want);
+    // the strict positions as two-bit counts per side (slidecore.hpp FAST): wherever that form applies it runs too, beside the per-position form
+    uint32_t fp, rp;
+    const bool fast = only_simple && slide_strict_lists(C.k, C.sF, C.sR, fp, rp);
+#define RUN(LV, G, F) (gw == 1 ? run_plan<LV, 1>(C, P, G, only_simple, use_valid, F) : (gw == 2 ? run_plan<LV, 2>(C, P, G, only_simple, use_valid, F) : run_plan<LV, 4>(C, P, G, only_simple, use_valid, F)))
+    for (int f = with_slow ? 0 : 1; f <= (fast ? 1 : 0); f++) {
+        std::vector<long long> &g = f ? got_fast : got;
+        switch (C.v) {
+            case 0: RUN(1, g, f); break;
+            case 1: RUN(2, g, f); break;
+            case 2: RUN(3, g, f); break;
+            default: RUN(4, g, f); break;
+        }
+    }
+#undef RUN
+    if (!with_slow) got = got_fast;
+    if (fast) { T.n_fast++; if (got_fast != got) { fprintf(stderr, "trial %d: k=%d v=%d sF=%x sR=%x: the two strict forms differ\n", trial, C.k, C.v, C.sF, C.sR); return 1; } }
+    // candidates of the items the builder left to the first-pass kernels are not the plan's to count
+    for (size_t ci = 0; ci < C.chains.size(); ci++) {
+        if (P.slides[ci]) { T.items_slid++; continue; }
+        T.items_rest++;
+        for (int t = 0; t < C.chains[ci].n_steps; t++) {
+            const int32_t oc = C.cand_out[(size_t)C.chains[ci].cand0 + (size_t)t];
+            for (int r = 0; r < 3; r++) want[(size_t)oc * 3 + r] = 0;
+        }
+    }
+    if (want != got) {
+        size_t bad = 0;
+        for (size_t i = 0; i < want.size(); i++)
+            if (want[i] != got[i]) { bad = i; break; }
+        fprintf(stderr, "trial %d: k=%d v=%d rows=%d bands=%zu B=%d: candidate %zu counter %zu: brute %lld, plan %lld\n", trial, C.k, C.v,
+                C.n_rows, P.bands.size(), B, bad / 3, bad % 3, want[bad], got[bad]);
+        return 1;
+    }
+    return 0;
+}
+
+// slide_emul [trials [seed]]                                      random shapes
+// slide_emul ring K V ROWS BAND GW SF SR STRICT [seed]            one shape (SF, SR: strict masks in hex; STRICT=0: the per-position form only, as
+//                                                                  MP_SLIDE_STRICT=0): the GPU kernel's form (simple items, every row counted), windows
+//                                                                  without chains inside the bands
 int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "ring") {
+        if (argc < 10) { fprintf(stderr, "slide_emul ring K V ROWS BAND GW SF SR STRICT [seed]\n"); return 2; }
+        const int B = atoi(argv[5]), gw = atoi(argv[6]), strict = atoi(argv[9]);
+        const Fixed fx{atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), B, (uint32_t)strtoul(argv[7], nullptr, 16), (uint32_t)strtoul(argv[8], nullptr, 16)};
+        if (fx.k < 2 || fx.k > 31 || fx.v < 0 || fx.v > 3 || fx.k <= fx.v || fx.rows < 1 || B < 1 || (gw != 1 && gw != 2 && gw != 4)) { fprintf(stderr, "slide_emul ring: a shape the emulation does not take\n"); return 2; }
+        std::mt19937 rng(argc > 10 ? (unsigned)atoi(argv[10]) : 99u);
+        Tally T;
+        for (int trial = 0; trial < 3; trial++) {
+            Case C;
+            make_case(C, rng, 2, &fx);                                 // (an even trial: no seed off the consensus)
+            uint32_t fp, rp;
+            const bool lists = slide_strict_lists(C.k, C.sF, C.sR, fp, rp);
+            // (STRICT=1 on lists the two-bit form takes: that form alone — the per-position form is the STRICT=0 run)
+            if (check_case(C, B, true, false, gw, trial, !(strict && lists), T)) return 1;
+            if (!strict) T.n_fast = 0;
+        }
+        printf("slide_emul ring: %d cases equal to brute force (%lld items slid, %lld left out; %d in the two-bit strict form)\n", T.slid, T.items_slid, T.items_rest, T.n_fast);
+        // six windows of seven have one or two chains and every case has more than B + 8 windows: fewer than 3 x 6 / 7 x (B + 8) items that
+        // slid, or one in ten left out, means that the run checked windows without items
+        if (T.slid < 3 || T.items_slid * 7 < 18LL * (B + 8) || T.items_rest * 10 > T.items_slid) { fprintf(stderr, "slide_emul ring: too few items slid\n"); return 2; }
+        return 0;
+    }
     const int trials = argc > 1 ? atoi(argv[1]) : 300;
     std::mt19937 rng(argc > 2 ? (unsigned)atoi(argv[2]) : 12345u);
-    int slid = 0, refused = 0, n_fast = 0;
-    long long items_slid = 0, items_rest = 0;
+    Tally T;
     for (int trial = 0; trial < trials; trial++) {
         Case C;
         make_case(C, rng, trial);
         if (C.chains.empty()) continue;
-        SlidePlan P;
         const int B = 1 + (int)(rng() % 40);
         const bool only_simple = trial & 1;
         const bool use_valid = !only_simple || (trial & 2) || C.k <= C.v;             // without: the GPU kernel's form, every row of the alignment counts
-        if (!use_valid)
-            for (auto &w : C.valid) w = 0xFFFFFFFFu;                       // (rows past n_rows are all gaps: they never reach a count)
-        if (!build_slide_plan(C.chains, C.events, C.cand_out, C.k, C.sF, C.sR, C.p0, C.n_cols, B, 1u, only_simple, P)) { refused++; continue; }
-        P.iters.resize(P.iters.size() + 64, 0u);                          // as upload_eval_slide pads it
-        slid++;
-        std::vector<long long> want, got, got_fast;
-        brute(C, want);
         const int gw = 1 << (int)(rng() % 3);
-        // the strict positions as two-bit counts per side (slidecore.hpp FAST): wherever that form applies it runs too, beside the per-position form
-        uint32_t fp, rp;
-        const bool fast = only_simple && slide_strict_lists(C.k, C.sF, C.sR, fp, rp);
-#define RUN(LV, G, F) (gw == 1 ? run_plan<LV, 1>(C, P, G, only_simple, use_valid, F) : (gw == 2 ? run_plan<LV, 2>(C, P, G, only_simple, use_valid, F) : run_plan<LV, 4>(C, P, G, only_simple, use_valid, F)))
-        for (int f = 0; f <= (fast ? 1 : 0); f++) {
-            std::vector<long long> &g = f ? got_fast : got;
-            switch (C.v) {
-                case 0: RUN(1, g, f); break;
-                case 1: RUN(2, g, f); break;
-                case 2: RUN(3, g, f); break;
-                default: RUN(4, g, f); break;
-            }
-        }
-#undef RUN
-        if (fast) { n_fast++; if (got_fast != got) { fprintf(stderr, "trial %d: k=%d v=%d sF=%x sR=%x: the two strict forms differ\n", trial, C.k, C.v, C.sF, C.sR); return 1; } }
-        // candidates of the items the builder left to the first-pass kernels are not the plan's to count
-        for (size_t ci = 0; ci < C.chains.size(); ci++) {
-            if (P.slides[ci]) { items_slid++; continue; }
-            items_rest++;
-            for (int t = 0; t < C.chains[ci].n_steps; t++) {
-                const int32_t oc = C.cand_out[(size_t)C.chains[ci].cand0 + (size_t)t];
-                for (int r = 0; r < 3; r++) want[(size_t)oc * 3 + r] = 0;
-            }
-        }
-        if (want != got) {
-            size_t bad = 0;
-            for (size_t i = 0; i < want.size(); i++)
-                if (want[i] != got[i]) { bad = i; break; }
-            fprintf(stderr, "trial %d: k=%d v=%d rows=%d bands=%zu B=%d: candidate %zu counter %zu: brute %lld, plan %lld\n", trial, C.k, C.v,
-                    C.n_rows, P.bands.size(), B, bad / 3, bad % 3, want[bad], got[bad]);
-            return 1;
-        }
+        if (check_case(C, B, only_simple, use_valid, gw, trial, true, T)) return 1;
     }
     printf("slide_emul: %d cases equal to brute force (%lld items slid, %lld left to the first-pass kernels; %d cases also in the two-bit strict form), %d cases without a plan\n",
-           slid, items_slid, items_rest, n_fast, refused);
-    return slid > 0 ? 0 : 2;
+           T.slid, T.items_slid, T.items_rest, T.n_fast, T.refused);
+    return T.slid > 0 ? 0 : 2;
 }
