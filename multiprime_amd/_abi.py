@@ -156,6 +156,22 @@ STAR_MAX_ROUNDS = 8                 # MP_STAR_MAX_ROUNDS
 STAR_META = ANCHOR_META + 1         # MP_STAR_META
 STAR_COUNTS = 6                     # MP_STAR_COUNTS
 
+# include/mprime_ani.h: sketches and their comparison per pair of groups on the device (csrc/ani.hip) — exported by libmprime_hip.so only;
+# the checker of these calls is the plain restatement of the rule in tests/ani_ref.py
+ANI_SYMBOLS = [
+    ("mp_ani_sketch", C.c_int, [_p, C.c_int32, _p, _p, C.c_int32]),
+    ("mp_ani_sketches", C.c_int, [_p, _p, _p]),
+    ("mp_ani_pairs", C.c_int, [_p, C.c_int64, _p, _p, _p]),
+    ("mp_ani_groups", C.c_int, [_p, C.c_int32, _p, C.c_int64, _p, _p, C.c_int32, _p]),
+    ("mp_ani_table", C.c_int, [_p]),
+    ("mp_ani_stats", C.c_int, [_p, _p, _p]),
+]
+ANI_MIN_SKETCH = 16                 # MP_ANI_MIN_SKETCH
+ANI_MAX_SKETCH = 1024               # MP_ANI_MAX_SKETCH
+ANI_TABLE = 1025                    # MP_ANI_TABLE
+ANI_PAIR = 3                        # MP_ANI_PAIR
+ANI_PPM = 1000000                   # MP_ANI_PPM
+
 
 def prefer_staged_copies():
     """For the drop-in command lines, called before anything starts the HIP runtime: read-backs into ordinary numpy arrays go
@@ -257,9 +273,12 @@ class Library:
         self.star = all(hasattr(self.dll, name) for name, _, _ in STAR_SYMBOLS)
         if self.backend == "hip" and not self.star:
             raise MprimeError(-2, f"{path} lacks the star-alignment entry points of include/mprime_star.h: rebuild it")
+        self.ani = all(hasattr(self.dll, name) for name, _, _ in ANI_SYMBOLS)
+        if self.backend == "hip" and not self.ani:
+            raise MprimeError(-2, f"{path} lacks the identity-merge entry points of include/mprime_ani.h: rebuild it")
         for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
-                                (STAR_SYMBOLS if self.star else [])):
+                                (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -269,6 +288,16 @@ class Library:
 
     def context(self, device: int = 0) -> "Context":
         return Context(self, device)
+
+    def ani_table(self) -> np.ndarray:
+        """int32 [ANI_TABLE]: TAB of include/mprime_ani.h (mp_ani_table; needs no device)."""
+        if not self.ani:
+            raise MprimeError(-2, f"{self.path} does not serve include/mprime_ani.h (libmprime_hip.so does)")
+        out = np.zeros(ANI_TABLE, np.int32)
+        rc = self.dll.mp_ani_table(_ptr(out))
+        if rc != 0:
+            raise MprimeError(rc, "mp_ani_table")
+        return out
 
 
 def _ptr(a):
@@ -943,6 +972,61 @@ class Context:
         self._need_star()
         self._ck(self.d.mp_star_free(self.h))
         self.star_n = self.star_width = 0
+
+    # include/mprime_ani.h
+    def _need_ani(self):
+        if not self.lib.ani:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_ani.h (libmprime_hip.so does)")
+
+    def ani_sketch(self, data, off, s: int = ANI_MAX_SKETCH):
+        """Sketch the sequences data[off[i]:off[i+1]] at size s and keep the sketches resident (mp_ani_sketch)."""
+        self._need_ani()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        rc = self.d.mp_ani_sketch(self.h, len(off) - 1, _ptr(data), _ptr(off), int(s))
+        if rc != 0 and rc != -1:                # (MP_ERR_ARG: refused before anything was touched, the earlier set stays resident)
+            self.ani_n = 0
+        self._ck(rc)
+        self.ani_n, self.ani_s = len(off) - 1, int(s)
+
+    def ani_sketches(self):
+        """(hashes uint32 [n][s], sizes int32 [n]) of the resident sketches; a sketch is hashes[i, :sizes[i]] (mp_ani_sketches)."""
+        self._need_ani()
+        n, s = getattr(self, "ani_n", 0), getattr(self, "ani_s", 0)
+        hashes, sizes = np.zeros((max(n, 1), max(s, 1)), np.uint32), np.zeros(max(n, 1), np.int32)
+        self._ck(self.d.mp_ani_sketches(self.h, _ptr(hashes), _ptr(sizes)))
+        return hashes[:n], sizes[:n]
+
+    def ani_pairs(self, a_idx, b_idx) -> np.ndarray:
+        """int32 [n_pairs][ANI_PAIR] = w, u, ani_ppm of sketch a_idx[p] against sketch b_idx[p] (mp_ani_pairs)."""
+        self._need_ani()
+        a_idx = np.ascontiguousarray(a_idx, dtype=np.int32)
+        b_idx = np.ascontiguousarray(b_idx, dtype=np.int32)
+        out = np.zeros((max(len(a_idx), 1), ANI_PAIR), np.int32)
+        self._ck(self.d.mp_ani_pairs(self.h, len(a_idx), _ptr(a_idx), _ptr(b_idx), _ptr(out)))
+        return out[: len(a_idx)]
+
+    def ani_groups(self, group_off, q_group, r_group, report_ppm: int = 700000) -> np.ndarray:
+        """int64 [n_gp][2] = n_rep, sum_ppm of group q_group[x] against group r_group[x]; group g is the resident sequences
+        group_off[g] .. group_off[g+1] (mp_ani_groups)."""
+        self._need_ani()
+        group_off = np.ascontiguousarray(group_off, dtype=np.int32)
+        q_group = np.ascontiguousarray(q_group, dtype=np.int32)
+        r_group = np.ascontiguousarray(r_group, dtype=np.int32)
+        out = np.zeros((max(len(q_group), 1), 2), np.int64)
+        self._ck(self.d.mp_ani_groups(self.h, len(group_off) - 1, _ptr(group_off), len(q_group), _ptr(q_group), _ptr(r_group), int(report_ppm),
+                                      _ptr(out)))
+        return out[: len(q_group)]
+
+    def ani_table(self) -> np.ndarray:
+        return self.lib.ani_table()
+
+    def ani_stats(self):
+        """({sketch, compare}_ms, {sketches, pairs}): device event times of the last ani_sketch and of the comparisons since."""
+        self._need_ani()
+        ms, counts = np.zeros(2, np.float64), np.zeros(2, np.int64)
+        self._ck(self.d.mp_ani_stats(self.h, _ptr(ms), _ptr(counts)))
+        return dict(zip(("sketch_ms", "compare_ms"), ms.tolist())), dict(zip(("sketches", "pairs"), counts.tolist()))
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

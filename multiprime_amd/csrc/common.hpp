@@ -301,6 +301,13 @@ struct mp_ctx {
     std::vector<int64_t> cl_off_host;
     double cl_ms[5] = {0, 0, 0, 0, 0};
     int64_t cl_counts[3] = {0, 0, 0};
+    // merging by identity (ani.hip, include/mprime_ani.h): the sketches of mp_ani_sketch, TAB, and the times / counts since
+    uint32_t *ani_sk = nullptr;              // [ani_n][ani_s] ascending, 0xFFFFFFFF past a sketch's size
+    int32_t *ani_sizes = nullptr;            // [ani_n]
+    uint32_t *ani_tab = nullptr;             // [MP_ANI_TABLE]
+    int32_t ani_n = 0, ani_s = 0;
+    double ani_ms[2] = {0, 0};
+    int64_t ani_counts[2] = {0, 0};
     // star alignment (star.hip, include/mprime_star.h): the records of mp_star_load, the last round's path store, columns, rows and counts
     uint8_t *st_bytes = nullptr;             // [st_total] the records' letters as given, back to back
     int64_t *st_off = nullptr;               // [st_n + 1]
@@ -428,6 +435,7 @@ void free_seq(mp_ctx *c);        // scan.hip
 void free_anchor(mp_ctx *c);     // anchor.hip
 void free_cluster(mp_ctx *c);    // cluster.hip
 void free_star(mp_ctx *c);       // star.hip
+void free_ani(mp_ctx *c);        // ani.hip
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

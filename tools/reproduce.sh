@@ -202,5 +202,11 @@ star)            # profiles/star_msa.txt and profiles/star_scale.txt: the star a
   timeout -k 10 600 python -m pytest tests/test_star_gpu.py -x -q -s -m gpu 2>&1 | tee $O/star_msa.txt | tail -4 &&
   timeout -k 10 1100 python tools/star_bench.py --out $O/star_scale.txt &&
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_star -- python tools/star_bench.py --no-cluster --records 1000000 --repeats 0 2>&1 | tail -5 ;;
+ani)             # profiles/ani_merge.txt: the identity merge on 2000 synthetic clusters (1500 rare, records of 1 .. 10 kb, -t 20, s = 1024): sketch ms, compare ms, sequence pairs/s; then the yardstick's identity table (host only)
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_ani_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 600 python tools/ani_bench.py run 2>&1 | tee $O/ani_merge.txt &&
+  timeout -k 10 300 python tools/ani_bench.py table 2>&1 | tee -a $O/ani_merge.txt ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
