@@ -171,6 +171,27 @@ ANI_MAX_SKETCH = 1024               # MP_ANI_MAX_SKETCH
 ANI_TABLE = 1025                    # MP_ANI_TABLE
 ANI_PAIR = 3                        # MP_ANI_PAIR
 ANI_PPM = 1000000                   # MP_ANI_PPM
+# include/mprime_dege.h: DegePrime's degenerate oligomer per window on the device (csrc/dege.hip) — exported by libmprime_hip.so only; the
+# checker of these calls is the plain restatement of the rule in tests/dege_ref.py
+DEGE_SYMBOLS = [
+    ("mp_dege_load", C.c_int, [_p, C.c_int32, C.c_int32, _p]),
+    ("mp_dege_windows", C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("mp_dege_window_table", C.c_int, [_p, _p, _p]),
+    ("mp_dege_unique", C.c_int, [_p, C.c_int32, C.c_int64, _p, _p]),
+    ("mp_dege_merge", C.c_int, [_p, C.c_int32, C.c_int32, C.c_uint64]),
+    ("mp_dege_best", C.c_int, [_p, _p]),
+    ("mp_dege_iterations", C.c_int, [_p, C.c_int32, _p]),
+    ("mp_dege_stats", C.c_int, [_p, _p, _p]),
+]
+DEGE_MIN_L, DEGE_MAX_L = 2, 32      # MP_DEGE_MIN_L, MP_DEGE_MAX_L
+DEGE_MAX_DRAWS = 100                # MP_DEGE_MAX_DRAWS
+DEGE_MAX_ITERS = 65536              # MP_DEGE_MAX_ITERS
+DEGE_LDS_SLOTS = 4096               # MP_DEGE_LDS_SLOTS
+DEGE_LDS_LIMIT = 3072               # MP_DEGE_LDS_LIMIT: more distinct mers in a window take the global-memory table
+DEGE_SORT_MIN = 64                  # MP_DEGE_SORT_MIN: the sort sizes are the powers of two from here
+DEGE_MERGE_LDS = 4096               # MP_DEGE_MERGE_LDS: more unique mers in a window are merged from global memory
+DEGE_WIN = 4                        # MP_DEGE_WIN
+DEGE_REC = 35                       # MP_DEGE_REC
 
 
 def prefer_staged_copies():
@@ -276,9 +297,13 @@ class Library:
         self.ani = all(hasattr(self.dll, name) for name, _, _ in ANI_SYMBOLS)
         if self.backend == "hip" and not self.ani:
             raise MprimeError(-2, f"{path} lacks the identity-merge entry points of include/mprime_ani.h: rebuild it")
+        self.dege = all(hasattr(self.dll, name) for name, _, _ in DEGE_SYMBOLS)
+        if self.backend == "hip" and not self.dege:
+            raise MprimeError(-2, f"{path} lacks the DegePrime entry points of include/mprime_dege.h: rebuild it")
         for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
-                                (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else [])):
+                                (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else []) +
+                                (DEGE_SYMBOLS if self.dege else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -1027,6 +1052,69 @@ class Context:
         ms, counts = np.zeros(2, np.float64), np.zeros(2, np.int64)
         self._ck(self.d.mp_ani_stats(self.h, _ptr(ms), _ptr(counts)))
         return dict(zip(("sketch_ms", "compare_ms"), ms.tolist())), dict(zip(("sketches", "pairs"), counts.tolist()))
+
+    # include/mprime_dege.h
+    def _need_dege(self):
+        if not self.lib.dege:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_dege.h (libmprime_hip.so does)")
+
+    def dege_load(self, rows):
+        """Upload a trimmed alignment: rows uint8 [n_rows][width] (mp_dege_load)."""
+        self._need_dege()
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        if rows.ndim != 2:
+            raise ValueError("dege_load: rows must be a matrix of bytes")
+        self.dege_n_win = self.dege_iters = 0
+        self._ck(self.d.mp_dege_load(self.h, rows.shape[0], rows.shape[1], _ptr(rows)))
+
+    def dege_windows(self, l: int, skip: int = 20, depth: int = 1):
+        """(nums int32 [W][DEGE_WIN] = NumberSpanning, Z, UniqueMers, printed; entropy float64 [W]) of every window (mp_dege_windows,
+        mp_dege_window_table)."""
+        self._need_dege()
+        n = C.c_int32(0)
+        self.dege_n_win = self.dege_iters = 0
+        self._ck(self.d.mp_dege_windows(self.h, int(l), int(skip), int(depth), C.byref(n)))
+        self.dege_n_win = n.value
+        nums, ent = np.zeros((n.value, DEGE_WIN), np.int32), np.zeros(n.value, np.float64)
+        self._ck(self.d.mp_dege_window_table(self.h, _ptr(nums), _ptr(ent)))
+        self.dege_nums = nums
+        return nums, ent
+
+    def dege_unique(self, pos: int):
+        """(words uint64 [U] ascending, counts int32 [U]) of window pos (mp_dege_unique)."""
+        self._need_dege()
+        if not 0 <= pos < getattr(self, "dege_n_win", 0):
+            raise MprimeError(-1, f"dege_unique: window {pos} of {getattr(self, 'dege_n_win', 0)}")
+        u = int(self.dege_nums[pos, 2])
+        words, counts = np.zeros(u, np.uint64), np.zeros(u, np.int32)
+        self._ck(self.d.mp_dege_unique(self.h, int(pos), u, _ptr(words), _ptr(counts)))
+        return words, counts
+
+    def dege_merge(self, max_deg: int, iters: int = 100, seed: int = 0) -> np.ndarray:
+        """int32 [W][DEGE_REC] = match, deg, iteration, sets[32] of every window's winning iteration, -1 where the window is not printed
+        (mp_dege_merge, mp_dege_best)."""
+        self._need_dege()
+        if not 1 <= int(max_deg) <= 0x7FFFFFFF:
+            raise MprimeError(-1, f"dege_merge: maximum degeneracy {max_deg} (1..2147483647)")
+        self._ck(self.d.mp_dege_merge(self.h, int(max_deg), int(iters), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
+        self.dege_iters = int(iters)
+        out = np.zeros((self.dege_n_win, DEGE_REC), np.int32)
+        self._ck(self.d.mp_dege_best(self.h, _ptr(out)))
+        return out
+
+    def dege_iterations(self, pos: int) -> np.ndarray:
+        """int32 [iters][DEGE_REC] = deg, match, n_draws, sets[32] of every iteration of one printed window (mp_dege_iterations)."""
+        self._need_dege()
+        out = np.zeros((getattr(self, "dege_iters", 0), DEGE_REC), np.int32)
+        self._ck(self.d.mp_dege_iterations(self.h, int(pos), _ptr(out)))
+        return out
+
+    def dege_stats(self):
+        """({window, merge}_ms, {windows, printed, unique, global_windows}): device event times and counts of the last calls."""
+        self._need_dege()
+        ms, counts = np.zeros(2, np.float64), np.zeros(4, np.int64)
+        self._ck(self.d.mp_dege_stats(self.h, _ptr(ms), _ptr(counts)))
+        return dict(zip(("window_ms", "merge_ms"), ms.tolist())), dict(zip(("windows", "printed", "unique", "global_windows"), counts.tolist()))
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

@@ -53,6 +53,7 @@ struct ChainItem {
 };
 
 struct SlideBand;
+struct DegeState;
 
 // up to 16 * NQ symbol codes, one nibble each (position j = nibble j & 15 of word j >> 4).  NQ = 2: the k-mers of 32-bit window
 // words (the code of rounds 1-3, two named halves); NQ = 4: primers of 32..63 bases — the word index is a run-time value there, taken
@@ -324,6 +325,8 @@ struct mp_ctx {
     int32_t *st_colcnt = nullptr;            // [st_width][6]
     double st_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t st_counts[6] = {0, 0, 0, 0, 0, 0};
+    // DegePrime's oligomers per window (dege.hip, include/mprime_dege.h): the alignment, the windows and the result of the merging
+    mp::DegeState *dege = nullptr;
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run
@@ -436,6 +439,7 @@ void free_anchor(mp_ctx *c);     // anchor.hip
 void free_cluster(mp_ctx *c);    // cluster.hip
 void free_star(mp_ctx *c);       // star.hip
 void free_ani(mp_ctx *c);        // ani.hip
+void free_dege(mp_ctx *c);       // dege.hip
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

@@ -208,5 +208,12 @@ ani)             # profiles/ani_merge.txt: the identity merge on 2000 synthetic 
   timeout -k 10 300 python -m pytest tests/test_ani_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
   timeout -k 10 600 python tools/ani_bench.py run 2>&1 | tee $O/ani_merge.txt &&
   timeout -k 10 300 python tools/ani_bench.py table 2>&1 | tee -a $O/ani_merge.txt ;;
+dege)            # profiles/dege.txt: DegePrime on the recorded 150 x 320 slice and on a synthetic 10^5 x 1000 alignment: stage ms from mp_dege_stats, wall time; then the kernels' shares (kernel trace of the same program, a run of its own)
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_dege_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 600 python tools/dege_bench.py 2>&1 | tee $O/dege.txt &&
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof/trace -o t -- python tools/dege_bench.py > /dev/null 2>&1 &&
+  python tools/summarize_profile.py $O/prof 2>/dev/null | head -14 | tee -a $O/dege.txt ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
