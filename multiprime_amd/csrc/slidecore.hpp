@@ -78,6 +78,27 @@ SLIDE_HD void slide_pin(uint32_t &x) {
 #endif
 }
 
+// A register that holds nothing yet: the table word of a member slot the walk did not reach.  The commit reduces all twelve registers
+// of an item whatever the item's length, and nobody reads the word of a slot the item does not have, so any value will do — on the device
+// the register's old content (no instruction, and no move where the paths of the early exits meet: a zero would be written in front of
+// every exit test), on the host a pattern no count can take, which the emulation looks for under the slots the members report.
+constexpr uint32_t kSlideHole = 0xFFFFFFFFu;
+SLIDE_HD void slide_hole(uint32_t &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "=v"(x));
+#else
+    x = kSlideHole;
+#endif
+}
+
+// The walk of slide_item ends at the item's last member slot: SLIDE_WALK_EXIT names the slots IN FRONT of which the wave-uniform test
+// `slot >= n_slots` stands.  1 (default): every slot; 0: none — all eight slots, straight-line, as before; any other value: bit s = a test
+// in front of slot s (testing less often is always correct: the walk goes on to the next test over all-zero planes).
+#ifndef SLIDE_WALK_EXIT
+#define SLIDE_WALK_EXIT 1
+#endif
+constexpr uint32_t kSlideExitAt = SLIDE_WALK_EXIT == 1 ? 0xFEu : ((uint32_t)(SLIDE_WALK_EXIT) & 0xFEu);
+
 // 5-bit bit-sliced counters (k <= 31 columns): c += up - down for two disjoint one-bit planes given as (changed, direction):
 // x = rows that change, dir = rows that go UP among them (rows of x outside dir go down).  10 instructions per word.
 struct SlideCount { uint32_t b0, b1, b2, b3, b4; };
@@ -158,8 +179,9 @@ SLIDE_HD void slide_request(Env &env, const typename Env::Rec &rec, SlideFetch<G
     for (int s = 1; s <= kSlideKept; s++) env.fetch_event(env.rec_word(rec, s), F.d[s]);
 }
 
-// One item: all eight member slots, straight-line (a slot the item does not have repeats the counts of the one before it — its plane
-// is the all-zero row — and reports to nobody).  SIMPLE (the host's flag; every chain of a refinement run has it): every event plane is
+// One item: its member slots one after the other, up to the item's last one (header: n_slots; the slots behind it report to nobody — they
+// are not walked, their table words are holes: slide_hole.  Where no exit test stands, SLIDE_WALK_EXIT, such a slot repeats the counts of
+// the one before it: its plane is the all-zero row).  SIMPLE (the host's flag; every chain of a refinement run has it): every event plane is
 // the plane of a base beyond the reference — no per-plane masks in the carry-save sum.
 // FAST (simple items of a launch with at most three strict positions per side): `sv` does not hold the reference's mismatch words position by
 // position but, per side, their SUM over the side's strict positions as a two-bit bit-sliced count (sv[0], sv[1]: forward; sv[2], sv[3]:
@@ -291,8 +313,19 @@ SLIDE_HD void slide_item(Env &env, const SlideArgs &A, const typename Env::Rec &
     }
     // (c) walk down the chain: event plane s, then member slot s is counted.  Counts leave in the layout the wave sums want:
     // accPF[s] = out1 | outF << 16, accR[s / 2] = outR of an even slot | outR of the odd one << 16
+    // The walk stops in front of the first slot the item does not have (one taken branch per item, to the commit; slot 0 always is).  The
+    // slots behind it are a suffix, so an odd slot that was walked never shares its accR word with an even one that was not: the even slot
+    // of a word writes it whole, the odd one ORs into it.
+    const int n_slots = (int)(hdr & 255u);
+    if (kSlideExitAt) {
+#pragma unroll
+        for (int s = 1; s < 8; s++) slide_hole(accPF[s]);
+#pragma unroll
+        for (int q = 1; q < 4; q++) slide_hole(accR[q]);
+    }
 #pragma unroll
     for (int s = 0; s < 8; s++) {
+        if (((kSlideExitAt >> s) & 1u) && s >= n_slots) break;
         if (s > 0) {
             // one more mismatch puts a row OUT when it already has v of them (T[LV - 2]; any row when v = 0) or the position is strict:
             // DF |= d & (T | strict), with the strict flag of the event as an all-ones / all-zeros scalar — no select, no branch
