@@ -46,7 +46,16 @@
  * m + n_del letters.
  *
  * Limits: query and anchor length 1 .. MP_ANCHOR_MAX_LEN each; scores are int32.  A seed alignment from nothing and an
- * anchor re-estimated from the added rows are mprime_star.h's.  Not attempted: reverse-complement queries, several GPUs.
+ * anchor re-estimated from the added rows are mprime_star.h's.  Not attempted: several GPUs.
+ *
+ * ORIENTATION (both strands; off unless mp_anchor_strands(ctx, 1) was called).  rc(s) is the upper-cased record reversed, each letter
+ * mapped A<>T, C<>G, R<>Y, K<>M, B<>V, D<>H, U->A; S, W, N and any other byte stay as they are.  Let (c+, d+) be the vote count and the
+ * diagonal of the best diagonal of the votes of q against the anchor, exactly as above, and (c-, d-) the same for rc(q).  The query
+ * is turned iff c- > c+, strictly: equal counts — no vote at all, a query under 12 bases, a query that is its own reverse complement
+ * — leave it as it stands.  From there on the query IS rc(q): d0, the alignment, the row's letters, the ops and the counts are those
+ * of the rule above applied to the oriented record.
+ *     status bit 3   (MP_ANCHOR_REVERSED) the row is that of the reverse complement of the input record
+ * (bit 2 is internal and never set in a record handed back.)
  */
 #ifndef MPRIME_ANCHOR_H
 #define MPRIME_ANCHOR_H
@@ -65,6 +74,7 @@ struct mp_ctx;
 #define MP_ANCHOR_WORD 12              /* letters of a vote word */
 #define MP_ANCHOR_NO_SCORE INT32_MIN   /* the band admits no alignment */
 #define MP_ANCHOR_META 10              /* int32 per meta record */
+#define MP_ANCHOR_REVERSED 8           /* status bit 3: the reverse complement of the input record was aligned */
 
 typedef struct mp_anchor_params {
     int32_t match, mismatch, gap_open, gap_extend;
@@ -94,6 +104,10 @@ int mp_anchor_set(struct mp_ctx *ctx, const uint8_t *anchor_codes, int32_t n, co
  * first empty or over-long query; nothing is launched then. */
 int mp_anchor_align(struct mp_ctx *ctx, int32_t n_queries, const uint8_t *bytes, const int64_t *off, int32_t want_ops,
                     uint8_t *rows_out, int32_t *meta_out, uint8_t *ops_out, const int64_t *ops_off);
+
+/* A switch of the context, read by mp_anchor_align and by mp_star_round (mprime_star.h): both != 0 votes both strands of every query
+ * and turns it as ORIENTATION says; 0 (the default) is the forward-only rule, with the kernels and results of before the switch existed. */
+int mp_anchor_strands(struct mp_ctx *ctx, int32_t both);
 
 /* Of the last mp_anchor_align of this context: ms[5] = {vote, DP, traceback + emit (device event times, summed over the batches),
  * read-back, whole call (host clock)}, counts[3] = {batches, DP cells, bytes of traceback bits of the largest batch}. */

@@ -34,8 +34,14 @@
  * 0 .. MP_ANCHOR_MAX_LEN.  A record whose 12-mers recur so often in a block of representatives that its vote table exceeds the
  * device budget (low-complexity repeats by the hundred thousand) is refused by name with MP_ERR_CAPACITY.
  *
- * Not attempted: reverse-complement hits (the pipeline's cd-hit call is forward-strand only), best-hit mode (cd-hit -g 1), several
- * GPUs.  A letter outside A/C/G/T never counts as a match, so at identity 1.0 a record containing N only ever founds its own cluster.
+ * BOTH STRANDS (mp_cluster_greedy_strands, mp_cluster_pairs_strands; what cd-hit-est does with -r 1).  rc(s) is mprime_anchor.h's: the
+ * record reversed and complemented; in the code store a code below 4 (A, C, G, T = 0 .. 3) becomes 3 - code and every other code
+ * stays.  similar+-(s, r): similar(s, r) is tested first and, if it holds, the strand is `+`; otherwise similar(rc(s), r) is tested
+ * and, if it holds, the strand is `-`.  A sequence joins the earliest-created representative for which either test holds; a
+ * representative always keeps its given orientation; n_match and the printed identity come from the strand that held.  Printed as
+ * `at +/dd.dd%` and `at -/dd.dd%`.  The forward-only calls are untouched by this.
+ *
+ * Not attempted: best-hit mode (cd-hit -g 1), several GPUs.  A letter outside A/C/G/T never counts as a match, so at identity 1.0 a record containing N only ever founds its own cluster.
  *
  * HOW IT RUNS (results do not depend on any of it)
  *
@@ -45,6 +51,9 @@
  * sequence is seeded and aligned against the block's real representatives; (4) it joins the smallest-numbered one that passes.
  * This equals the sequential rule for every B.  B is sized from free device memory (at most MP_CLUSTER_MAX_BLOCK);
  * MP_CLUSTER_BLOCK=<sequences> caps it and MP_CLUSTER_PAIR_BATCH=<pairs> caps the pairs of one alignment launch, both read per call.
+ * Both strands: the first both-strand call builds rc of every resident sequence on the device as sequence n + i of the same store
+ * (nothing is uploaded again; the store doubles until the next mp_cluster_load).  A seeding's queries are the forward copies and the
+ * reverse copies; the reverse copy of a pair is aligned only where the forward test of that pair did not hold.
  */
 #ifndef MPRIME_CLUSTER_H
 #define MPRIME_CLUSTER_H
@@ -89,6 +98,16 @@ int mp_cluster_pairs(struct mp_ctx *ctx, int64_t n_pairs, const int32_t *q_idx, 
  * length). */
 int mp_cluster_greedy(struct mp_ctx *ctx, const mp_cluster_params *params, int32_t *cluster_of, int32_t *rep_of_cluster,
                       int32_t *n_match_of, int32_t *n_clusters);
+
+/* mp_cluster_pairs with a strand per pair: q_strand[p] = 0 takes sequence q_idx[p] as the query, 1 takes rc of it; the anchor is
+ * always the sequence as given.  Records as in mp_cluster_pairs. */
+int mp_cluster_pairs_strands(struct mp_ctx *ctx, int64_t n_pairs, const int32_t *q_idx, const int32_t *r_idx, const int32_t *q_strand,
+                             const mp_cluster_params *params, int32_t *out);
+
+/* mp_cluster_greedy under BOTH STRANDS: strand_of[n] is 0 for a representative and for a member that joined as given, 1 for a member
+ * whose reverse complement joined (n_match_of is that strand's). */
+int mp_cluster_greedy_strands(struct mp_ctx *ctx, const mp_cluster_params *params, int32_t *cluster_of, int32_t *rep_of_cluster,
+                              int32_t *n_match_of, int32_t *strand_of, int32_t *n_clusters);
 
 /* Of the last mp_cluster_greedy / mp_cluster_pairs of this context: ms[5] = {block index, seed, alignment (device event times, summed
  * over the launches), host resolve, whole call (host clock)}, counts[3] = {rounds, candidate pairs aligned, DP cells}. */

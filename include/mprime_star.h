@@ -36,7 +36,13 @@
  * The output is the last round's alignment.  The round loop is the caller's (multiprime_amd/starmsa.py): mp_star_round is one round,
  * and the column counts it leaves are all the next anchor needs.
  *
- * Not attempted: reverse-complement records, progressive / guide-tree alignment, several GPUs.
+ * Both strands (mprime_anchor.h: ORIENTATION; on after mp_anchor_strands(ctx, 1)).  Every round votes both strands of each record AS
+ * IT IS CURRENTLY HELD and turns it iff the reverse complement's best diagonal has strictly more votes; a record that is turned stays
+ * turned for the later rounds (the resident bytes are rewritten once), and mp_star_load holds every record as given again.  Status
+ * bit 3 (MP_ANCHOR_REVERSED) of a round's meta record is the record's parity against the loaded record.  Round 0's centre is the
+ * longest record in its given orientation (the caller's choice of anchor).  Everything else of the rule applies to the oriented record.
+ *
+ * Not attempted: progressive / guide-tree alignment, several GPUs.
  */
 #ifndef MPRIME_STAR_H
 #define MPRIME_STAR_H

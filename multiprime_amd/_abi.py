@@ -120,6 +120,7 @@ ANCHOR_SYMBOLS = [
     ("mp_anchor_align", C.c_int, [_p, C.c_int32, _p, _p, C.c_int32, _p, _p, _p, _p]),
     ("mp_anchor_stats", C.c_int, [_p, _p, _p]),
 ]
+ANCHOR_REVERSED = 8                 # MP_ANCHOR_REVERSED
 ANCHOR_MAX_LEN = 32767              # MP_ANCHOR_MAX_LEN
 ANCHOR_MAX_BAND = 255               # MP_ANCHOR_MAX_BAND
 ANCHOR_MAX_PARAM = 4095             # MP_ANCHOR_MAX_PARAM
@@ -141,6 +142,12 @@ CLUSTER_SYMBOLS = [
     ("mp_cluster_stats", C.c_int, [_p, _p, _p]),
 ]
 CLUSTER_PAIR = 5                    # MP_CLUSTER_PAIR
+# both strands: mp_anchor_strands (read by mp_anchor_align and mp_star_round), the both-strand clustering calls
+STRAND_SYMBOLS = [
+    ("mp_anchor_strands", C.c_int, [_p, C.c_int32]),
+    ("mp_cluster_pairs_strands", C.c_int, [_p, C.c_int64, _p, _p, _p, C.POINTER(ClusterParams), _p]),
+    ("mp_cluster_greedy_strands", C.c_int, [_p, C.POINTER(ClusterParams), _p, _p, _p, _p, C.POINTER(C.c_int32)]),
+]
 
 # include/mprime_star.h: the star alignment on the device (csrc/star.hip) — exported by libmprime_hip.so only; the checker of these calls
 # is the plain restatement of the rule in tests/star_ref.py
@@ -294,6 +301,9 @@ class Library:
         self.star = all(hasattr(self.dll, name) for name, _, _ in STAR_SYMBOLS)
         if self.backend == "hip" and not self.star:
             raise MprimeError(-2, f"{path} lacks the star-alignment entry points of include/mprime_star.h: rebuild it")
+        self.strands = all(hasattr(self.dll, name) for name, _, _ in STRAND_SYMBOLS)
+        if self.backend == "hip" and not self.strands:
+            raise MprimeError(-2, f"{path} lacks the both-strand entry points of include/mprime_anchor.h and include/mprime_cluster.h: rebuild it")
         self.ani = all(hasattr(self.dll, name) for name, _, _ in ANI_SYMBOLS)
         if self.backend == "hip" and not self.ani:
             raise MprimeError(-2, f"{path} lacks the identity-merge entry points of include/mprime_ani.h: rebuild it")
@@ -303,7 +313,7 @@ class Library:
         for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
                                 (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else []) +
-                                (DEGE_SYMBOLS if self.dege else [])):
+                                (DEGE_SYMBOLS if self.dege else []) + (STRAND_SYMBOLS if self.strands else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -886,6 +896,14 @@ class Context:
                    for q in range(nq)]
         return rows[:nq], meta[:nq], ops
 
+    def anchor_strands(self, both: bool = True):
+        """Switch of the context (mp_anchor_strands): anchor_align and star_round vote both strands and turn a query once; meta status
+        bit 3 (ANCHOR_REVERSED) marks a turned one."""
+        self._need_anchor()
+        if not self.lib.strands:
+            raise MprimeError(-2, f"{self.lib.path} has no both-strand entry points")
+        self._ck(self.d.mp_anchor_strands(self.h, int(bool(both))))
+
     def anchor_stats(self):
         """Of the last anchor_align: ({vote, dp, trace, readback, call}_ms, {batches, cells, traceback_bytes})."""
         self._need_anchor()
@@ -932,6 +950,34 @@ class Context:
         par = self._cluster_params(band, identity_permille, min_votes, match, mismatch, gap_open, gap_extend)
         self._ck(self.d.mp_cluster_greedy(self.h, C.byref(par), _ptr(cluster_of), _ptr(rep), _ptr(n_match), C.byref(nc)))
         return cluster_of[:n], rep[: nc.value], n_match[:n]
+
+    def cluster_pairs_strands(self, q_idx, r_idx, q_strand, band: int = 32, identity_permille: int = 800, min_votes: int = 1, match: int = 5,
+                              mismatch: int = 4, gap_open: int = 10, gap_extend: int = 2):
+        """cluster_pairs with a strand per pair: q_strand[p] = 1 takes the reverse complement of q_idx[p] as the query (mp_cluster_pairs_strands)."""
+        self._need_cluster()
+        if not self.lib.strands:
+            raise MprimeError(-2, f"{self.lib.path} has no both-strand entry points")
+        q_idx, r_idx = np.ascontiguousarray(q_idx, dtype=np.int32), np.ascontiguousarray(r_idx, dtype=np.int32)
+        q_strand = np.ascontiguousarray(q_strand, dtype=np.int32)
+        if not len(q_idx) == len(r_idx) == len(q_strand):
+            raise ValueError("cluster_pairs_strands: q_idx, r_idx and q_strand differ in length")
+        out = np.zeros((max(len(q_idx), 1), CLUSTER_PAIR), np.int32)
+        par = self._cluster_params(band, identity_permille, min_votes, match, mismatch, gap_open, gap_extend)
+        self._ck(self.d.mp_cluster_pairs_strands(self.h, len(q_idx), _ptr(q_idx), _ptr(r_idx), _ptr(q_strand), C.byref(par), _ptr(out)))
+        return out[: len(q_idx)]
+
+    def cluster_greedy_strands(self, band: int = 32, identity_permille: int = 800, min_votes: int = 1, match: int = 5, mismatch: int = 4,
+                               gap_open: int = 10, gap_extend: int = 2):
+        """(cluster_of, rep_of_cluster, n_match_of, strand_of int32 [n]) under both strands (mp_cluster_greedy_strands)."""
+        self._need_cluster()
+        if not self.lib.strands:
+            raise MprimeError(-2, f"{self.lib.path} has no both-strand entry points")
+        n = getattr(self, "cluster_n", 0)
+        cluster_of, rep, n_match, strand = (np.zeros(max(n, 1), np.int32) for _ in range(4))
+        nc = C.c_int32(0)
+        par = self._cluster_params(band, identity_permille, min_votes, match, mismatch, gap_open, gap_extend)
+        self._ck(self.d.mp_cluster_greedy_strands(self.h, C.byref(par), _ptr(cluster_of), _ptr(rep), _ptr(n_match), _ptr(strand), C.byref(nc)))
+        return cluster_of[:n], rep[: nc.value], n_match[:n], strand[:n]
 
     def cluster_stats(self):
         """Of the last cluster_greedy / cluster_pairs: ({index, seed, dp, resolve, call}_ms, {rounds, pairs, cells})."""

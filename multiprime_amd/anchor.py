@@ -6,7 +6,9 @@ include/mprime_anchor.h and INTEGRATION.md).  The output is an ordinary aligned 
 
 writes OUT (the seed's records, then every accepted query as one line of L letters), OUT.anchor.tsv (one line per query) and
 OUT.unaligned.fa (the rejected queries as given).  Records are those of the FASTA front end every drop-in uses (msa.read_records):
-an id is the header's first token, '>' included.
+an id is the header's first token, '>' included.  `--adjust-direction` (mafft's --adjustdirection): a query whose reverse complement
+seeds better is turned; it is written under the id `_R_<id>`, its row is that of the reverse complement, and OUT.anchor.tsv gets a last
+column `strand`.  OUT.unaligned.fa keeps queries as given.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import time
 
 import numpy as np
 
-from ._abi import ANCHOR_MAX_BAND, ANCHOR_MAX_LEN, ANCHOR_MAX_PARAM, Library
+from ._abi import ANCHOR_MAX_BAND, ANCHOR_MAX_LEN, ANCHOR_MAX_PARAM, ANCHOR_REVERSED, Library
 
 META_FIELDS = ("score", "d0", "n_match", "n_ins", "n_del", "first_col", "last_col", "status", "first_anchor", "last_anchor")
 _UPPER = np.arange(256, dtype=np.uint8)
@@ -39,6 +41,11 @@ def anchor_of(seed_rows):
     return base[col].tobytes(), col
 
 
+def oriented_id(ident: str, reversed_: bool) -> str:
+    """mafft's name of a record it turned: `>_R_<id>`."""
+    return (">_R_" + ident[1:] if ident.startswith(">") else "_R_" + ident) if reversed_ else ident
+
+
 def _records(path, what):
     from .msa import read_records
     try:
@@ -52,7 +59,8 @@ def _records(path, what):
 
 class AnchoredAlignment:
     def __init__(self, seed_file, query_file, outfile, band=32, match=5, mismatch=4, gap_open=10, gap_extend=2, min_identity=0.5,
-                 keep_seed=True, device=0, library=None, want_ops=False):
+                 keep_seed=True, device=0, library=None, want_ops=False, adjust_direction=False):
+        self.adjust_direction = bool(adjust_direction)
         self.seed_file, self.query_file, self.outfile = seed_file, query_file, outfile
         self.band, self.match, self.mismatch, self.gap_open, self.gap_extend = int(band), int(match), int(mismatch), int(gap_open), int(gap_extend)
         self.min_identity_permille = int(round(float(min_identity) * 1000))
@@ -92,6 +100,8 @@ class AnchoredAlignment:
             raise RuntimeError(f"{lib.path} has no anchored alignment (include/mprime_anchor.h): there is no host fallback")
         ctx = lib.context(self.device)
         try:
+            if self.adjust_direction:
+                ctx.anchor_strands(True)
             ctx.anchor_set(self.anchor, self.col, self.width, band=self.band, match=self.match, mismatch=self.mismatch, gap_open=self.gap_open,
                            gap_extend=self.gap_extend, min_identity_permille=self.min_identity_permille)
             self._rows, self._meta, self._ops = ctx.anchor_align(self.qdata, self.qoff, want_ops=self.want_ops)
@@ -111,13 +121,15 @@ class AnchoredAlignment:
             for q0 in range(0, len(ok), 1 << 16):
                 parts = []
                 for q in np.flatnonzero(ok[q0:q0 + (1 << 16)]) + q0:
-                    parts.append(self._ids[q].encode())
+                    parts.append(oriented_id(self._ids[q], bool(self._meta[q, 7] & ANCHOR_REVERSED)).encode())
                     parts.append(self._rows[q].tobytes())
                 if parts:
                     fo.write(b"\n".join(parts) + b"\n")
         with open(self.outfile + ".anchor.tsv", "w") as fo:
-            fo.write("id\tstatus\tscore\td0\tn_match\tn_ins\tn_del\tfirst_col\tlast_col\n")
-            fo.writelines("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(self._ids[q], mt[7], mt[0], mt[1], mt[2], mt[3], mt[4], mt[5], mt[6])
+            strand = self.adjust_direction
+            fo.write("id\tstatus\tscore\td0\tn_match\tn_ins\tn_del\tfirst_col\tlast_col" + ("\tstrand\n" if strand else "\n"))
+            fo.writelines("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}{}\n".format(self._ids[q], mt[7], mt[0], mt[1], mt[2], mt[3], mt[4], mt[5], mt[6],
+                                                                          ("\t-" if mt[7] & ANCHOR_REVERSED else "\t+") if strand else "")
                           for q, mt in enumerate(self._meta.tolist()))
         with open(self.outfile + ".unaligned.fa", "wb") as fo:
             for q in np.flatnonzero(~ok):
@@ -172,6 +184,8 @@ def parse_args(argv=None):
     p.add_argument("--min-identity", type=float, default=0.5, metavar="<float>",
                    help="a query with fewer matching pairs than this share of its length goes to <out>.unaligned.fa. Default: 0.5")
     p.add_argument("--no-seed", action="store_true", help="do not repeat the seed's records in <out>")
+    p.add_argument("--adjust-direction", action="store_true", help="turn a query whose reverse complement seeds better (mafft --adjustdirection); "
+                   "it is written as _R_<id>. Default: queries are aligned as given")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal (default 0)")
     args = p.parse_args(argv)
     if not 0 <= args.band <= ANCHOR_MAX_BAND:
@@ -190,7 +204,8 @@ def main(argv=None):
     e1 = time.time()
     args = parse_args(argv)                     # exit status 2 on bad flags
     app = AnchoredAlignment(args.seed, args.input, args.out, band=args.band, match=args.match, mismatch=args.mismatch, gap_open=args.gap_open,
-                            gap_extend=args.gap_extend, min_identity=args.min_identity, keep_seed=not args.no_seed, device=args.device)
+                            gap_extend=args.gap_extend, min_identity=args.min_identity, keep_seed=not args.no_seed, device=args.device,
+                            adjust_direction=args.adjust_direction)
     try:
         app.run()                               # SystemExit with a message (status 1) on an unreadable or empty input
     except ValueError as e:

@@ -4,7 +4,8 @@ include/mprime_cluster.h and INTEGRATION.md).
 
     python scripts/cluster_by_identity.py -i in.fa -o out.fa -c 0.8
 
-writes OUT (the representatives' records in cluster order, upper-cased, one line each) and OUT.clstr in cd-hit's layout, which is what
+(`--both-strands`: a record may also join as its reverse complement, cd-hit-est's `-r 1`; member lines then read `at +/dd.dd%` or
+`at -/dd.dd%`) writes OUT (the representatives' records in cluster order, upper-cased, one line each) and OUT.clstr in cd-hit's layout, which is what
 extract_cluster.py parses.  Records are those of the FASTA front end every drop-in uses (msa.read_records): an id is the header's first
 token, '>' included.
 """
@@ -30,12 +31,12 @@ def identity_text(n_match: int, m: int) -> str:
 
 class ClusterByIdentity:
     def __init__(self, input, outfile, identity=0.8, band=32, min_votes=1, match=5, mismatch=4, gap_open=10, gap_extend=2, device=0,
-                 library=None):
+                 library=None, both_strands=False):
         self.input, self.outfile = input, outfile
         self.identity_permille = int(round(float(identity) * 1000))
         self.band, self.min_votes = int(band), int(min_votes)
         self.match, self.mismatch, self.gap_open, self.gap_extend = int(match), int(mismatch), int(gap_open), int(gap_extend)
-        self.device, self.library = device, library
+        self.device, self.library, self.both_strands = device, library, bool(both_strands)
         if not 0 <= self.identity_permille <= 1000:
             raise ValueError(f"identity {identity}: 0..1")
         if not 0 <= self.band <= ANCHOR_MAX_BAND:
@@ -46,7 +47,7 @@ class ClusterByIdentity:
             if not 0 <= getattr(self, name) <= ANCHOR_MAX_PARAM:
                 raise ValueError(f"{name} {getattr(self, name)}: 0..{ANCHOR_MAX_PARAM}")
         self.stats = {}
-        self._ids = self._cluster_of = self._reps = self._n_match = None
+        self._ids = self._cluster_of = self._reps = self._n_match = self._strand = None
 
     def _params(self):
         return dict(band=self.band, identity_permille=self.identity_permille, min_votes=self.min_votes, match=self.match, mismatch=self.mismatch,
@@ -75,7 +76,10 @@ class ClusterByIdentity:
         ctx = lib.context(self.device)
         try:
             ctx.cluster_load(self.data, self.off)
-            self._cluster_of, self._reps, self._n_match = ctx.cluster_greedy(**self._params())
+            if self.both_strands:
+                self._cluster_of, self._reps, self._n_match, self._strand = ctx.cluster_greedy_strands(**self._params())
+            else:
+                self._cluster_of, self._reps, self._n_match = ctx.cluster_greedy(**self._params())
             ms, counts = ctx.cluster_stats()
             self.stats.update(ms, **counts)
         finally:
@@ -93,7 +97,8 @@ class ClusterByIdentity:
             if k != last:
                 lines.append(">Cluster %d" % k)
                 last, x = k, 0
-            tail = "*" if is_rep[i] else "at " + identity_text(self._n_match[i], self.lens[i])
+            sign = ("-/" if self._strand[i] else "+/") if self.both_strands else ""
+            tail = "*" if is_rep[i] else "at " + sign + identity_text(self._n_match[i], self.lens[i])
             lines.append("%d\t%daa, %s... %s" % (x, self.lens[i], self._ids[i], tail))
             x += 1
         return "\n".join(lines) + "\n"
@@ -139,6 +144,12 @@ class ClusterByIdentity:
         self._ran()
         return self._n_match
 
+    @property
+    def strand(self):
+        """int32 [n]: 1 where a member joined as its reverse complement (representatives and forward members 0); None without both_strands."""
+        self._ran()
+        return self._strand
+
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Cluster sequences by identity (greedy incremental, cd-hit's .clstr layout) on the GPU")
@@ -147,6 +158,8 @@ def parse_args(argv=None):
     p.add_argument("-c", "--identity", type=float, default=0.8, metavar="<float>", help="identity threshold over the shorter sequence. Default: 0.8")
     p.add_argument("--band", type=int, default=32, metavar="<int>", help=f"half width W of the band around the seed diagonal, 0..{ANCHOR_MAX_BAND}. Default: 32")
     p.add_argument("--min-votes", type=int, default=1, metavar="<int>", help="shared 12-mers on the best diagonal a pair needs to be aligned. Default: 1")
+    p.add_argument("--both-strands", action="store_true", help="a record may join a cluster as its reverse complement (cd-hit-est -r 1); "
+                   "member lines read `at +/dd.dd%%` / `at -/dd.dd%%`. Default: forward strand only")
     p.add_argument("--match", type=int, default=5, metavar="<int>")
     p.add_argument("--mismatch", type=int, default=4, metavar="<int>")
     p.add_argument("--gap-open", type=int, default=10, metavar="<int>")
@@ -171,7 +184,8 @@ def main(argv=None):
     e1 = time.time()
     args = parse_args(argv)                     # exit status 2 on bad flags
     app = ClusterByIdentity(args.input, args.out, identity=args.identity, band=args.band, min_votes=args.min_votes, match=args.match,
-                            mismatch=args.mismatch, gap_open=args.gap_open, gap_extend=args.gap_extend, device=args.device)
+                            mismatch=args.mismatch, gap_open=args.gap_open, gap_extend=args.gap_extend, device=args.device,
+                            both_strands=args.both_strands)
     try:
         app.run()                               # SystemExit with a message (status 1) on an unreadable or empty input
     except ValueError as e:

@@ -161,16 +161,20 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
     int64_t *d_off = nullptr, *d_tboff = nullptr, *d_opsoff = nullptr;
     int32_t *d_d0 = nullptr, *d_end = nullptr, *d_meta = nullptr;
     uint32_t *d_tb = nullptr;
+    uint8_t *d_turn = nullptr;                 // both strands: 1 per query of the batch that anchor_orient_kernel turned
+    const bool both = c->an_both != 0;
     auto cleanup = [&]() {
         dev_free(c, &d_bytes, max_bytes); dev_free(c, &d_arow, max_q * n); dev_free(c, &d_rows, max_q * L); dev_free(c, &d_ops, max_ops);
         dev_free(c, &d_off, max_q + 1); dev_free(c, &d_tboff, max_q + 1); dev_free(c, &d_opsoff, max_q + 1); dev_free(c, &d_d0, max_q);
         dev_free(c, &d_end, 2 * max_q); dev_free(c, &d_meta, max_q * MP_ANCHOR_META); dev_free(c, &d_tb, max_tb);
+        dev_free(c, &d_turn, max_q);
     };
     int rc;
     if ((rc = dev_alloc(c, &d_bytes, max_bytes)) || (rc = dev_alloc(c, &d_arow, max_q * n)) || (rc = dev_alloc(c, &d_rows, max_q * L)) ||
         (rc = dev_alloc(c, &d_ops, max_ops)) || (rc = dev_alloc(c, &d_off, max_q + 1)) || (rc = dev_alloc(c, &d_tboff, max_q + 1)) ||
         (rc = dev_alloc(c, &d_opsoff, max_q + 1)) || (rc = dev_alloc(c, &d_d0, max_q)) || (rc = dev_alloc(c, &d_end, 2 * max_q)) ||
-        (rc = dev_alloc(c, &d_meta, max_q * MP_ANCHOR_META)) || (rc = dev_alloc(c, &d_tb, max_tb))) { cleanup(); return rc; }
+        (rc = dev_alloc(c, &d_meta, max_q * MP_ANCHOR_META)) || (rc = dev_alloc(c, &d_tb, max_tb)) ||
+        (both && (rc = dev_alloc(c, &d_turn, max_q)))) { cleanup(); return rc; }
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipError_t e = hipSuccess;
     for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
@@ -179,7 +183,8 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
     // LDS of a launch: the vote histogram of the longest query; the anchor and the queries of a workgroup's waves
     const size_t vote_lds = ((size_t)(max_m + n) / 2 + 1) * sizeof(uint32_t);
     if (vote_lds > 65536) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(anchor_vote_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vote_lds);
+        e = hipFuncSetAttribute(both ? reinterpret_cast<const void *>(anchor_orient_kernel<false>) : reinterpret_cast<const void *>(anchor_vote_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vote_lds);
         if (e != hipSuccess) return finish(fail(c, MP_ERR_DEVICE, "mp_anchor_align: %s", hipGetErrorString(e)));
     }
     const int npad = (n + 15) & ~15, mstride = (max_m + 15) & ~15;
@@ -203,8 +208,12 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
         if (e == hipSuccess && want_ops) e = hipMemcpyAsync(d_opsoff, h_opsoff.data(), sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(anchor_vote_kernel, dim3((unsigned)nb), dim3(64), vote_lds, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off, n,
-                           (const uint32_t *)c->an_kmer, (const int32_t *)c->an_table, log2_slots, d_d0);
+        if (both)          // the batch's device copy of the turned queries becomes rc(q): the sweep, the traceback and the emit read it as it is
+            hipLaunchKernelGGL(anchor_orient_kernel<false>, dim3((unsigned)nb), dim3(64), vote_lds, c->stream, d_bytes, (const int64_t *)d_off, n,
+                               (const uint32_t *)c->an_kmer, (const int32_t *)c->an_table, log2_slots, d_d0, d_turn);
+        else
+            hipLaunchKernelGGL(anchor_vote_kernel, dim3((unsigned)nb), dim3(64), vote_lds, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off, n,
+                               (const uint32_t *)c->an_kmer, (const int32_t *)c->an_table, log2_slots, d_d0);
         if ((e = hipGetLastError()) != hipSuccess) break;
         if ((e = hipEventRecord(ev[1], c->stream)) != hipSuccess) break;
         const dim3 grid((unsigned)((nb + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
@@ -222,6 +231,10 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
                            (const uint32_t *)d_tb, (const int64_t *)d_tboff, (const int32_t *)d_end, d_arow, d_meta, want_ops ? d_ops : (uint8_t *)nullptr,
                            (const int64_t *)d_opsoff, (const int32_t *)nullptr, 0LL, (uint16_t *)nullptr, (uint16_t *)nullptr, 0);
         if ((e = hipGetLastError()) != hipSuccess) break;
+        if (both) {
+            hipLaunchKernelGGL(anchor_mark_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, d_meta, (const uint8_t *)d_turn, (int)nb);
+            if ((e = hipGetLastError()) != hipSuccess) break;
+        }
         const long long total = (long long)nb * L;
         hipLaunchKernelGGL(anchor_emit_kernel, dim3((unsigned)((total + 4095) / 4096)), dim3(256), 0, c->stream, (const uint8_t *)d_arow,
                            (const int32_t *)d_meta, (const int32_t *)c->an_colinv, n, L, total, d_rows);
@@ -251,6 +264,12 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
     rc = finish(MP_OK);
     c->an_ms[4] = ms_since(t0);
     return rc;
+}
+
+int mp_anchor_strands(mp_ctx *c, int32_t both) {
+    if (!c) return MP_ERR_ARG;
+    c->an_both = both != 0;
+    return MP_OK;
 }
 
 int mp_anchor_stats(mp_ctx *c, double *ms, int64_t *counts) {

@@ -2,6 +2,8 @@
 // columns) and star.hip (rounds onto a re-estimated anchor, inserted bases kept).  Three kernels per batch of queries:
 //   anchor_vote_kernel   one wavefront per query: its 12-mers are looked up in the anchor's open-addressing table, the votes per
 //                        diagonal counted in an LDS histogram (two 16-bit counters per word), d0 chosen by a wave reduction
+//   anchor_orient_kernel its both-strand form (mp_anchor_strands): the same histogram for q and then for rc(q), the query's bytes
+//                        rewritten in place as rc(q) where that seeds better; anchor_mark_kernel sets status bit 3 afterwards
 //   anchor_dp_kernel     one wavefront per query, lanes own the band's diagonals (R = 1, 2, 4 or 8 neighbouring diagonals per lane for
 //                        2W + 1 <= 64 R).  ANTI-DIAGONAL sweep: at step s the cells with i + j = s are computed; cell (i, j) on diagonal
 //                        d reads its left cell (i, j-1) from diagonal d - 1 and its upper cell (i-1, j) from diagonal d + 1, both
@@ -76,6 +78,97 @@ __global__ __launch_bounds__(64) void anchor_vote_kernel(const uint8_t *__restri
         if (oc > 0 && (best_c == 0 || vote_better(oc, od, best_c, best_d))) { best_c = oc; best_d = od; }
     }
     if (lane == 0) d0_out[q] = best_c > 0 ? best_d : min(max(0, -m), n);
+}
+
+// ---- both strands (mprime_anchor.h: ORIENTATION) -------------------------------------------------------------------------------------
+// the complement of an upper-cased letter: A<>T, C<>G, R<>Y, K<>M, B<>V, D<>H, U->A; S, W, N and every other byte as they are
+__host__ __device__ inline uint8_t complement_letter(uint8_t ch) {
+    switch (ch) {
+        case 'A': return 'T'; case 'T': return 'A'; case 'U': return 'A'; case 'C': return 'G'; case 'G': return 'C';
+        case 'R': return 'Y'; case 'Y': return 'R'; case 'K': return 'M'; case 'M': return 'K';
+        case 'B': return 'V'; case 'V': return 'B'; case 'D': return 'H'; case 'H': return 'D';
+        default: return ch;
+    }
+}
+
+// One pass of the vote over the wave's histogram (cleared on entry, all lanes), kRev: over the words of rc(q), read from the forward
+// bytes — the word of rc(q) at i' = m - 12 - i is the window q[i .. i + 12) with its letters complemented and their order reversed, so
+// its bin is j - i' + m.  Returns the best (votes, diagonal) in every lane; votes 0: no vote.
+template <bool kRev>
+__device__ inline void orient_pass(uint32_t *hist, const uint8_t *qb, int m, int n, const uint32_t *__restrict__ akmer,
+                                   const int32_t *__restrict__ table, int log2_slots, int lane, int *best_c_out, int *best_d_out) {
+    const int words = (m + n) / 2 + 1;
+    for (int x = lane; x < words; x += 64) hist[x] = 0;
+    __syncthreads();
+    const uint32_t mask = (1u << log2_slots) - 1;
+    for (int i = lane; i + kWord <= m && n >= kWord; i += 64) {
+        uint32_t kmer = 0;
+        bool ok = true;
+        for (int x = 0; x < kWord; x++) {
+            const int cd = kRev ? base_code(complement_letter(upper_letter(qb[i + kWord - 1 - x]))) : base_code(qb[i + x]);
+            ok = ok && cd < 4;
+            kmer = (kmer << 2) | (uint32_t)(cd & 3);
+        }
+        if (!ok) continue;
+        const int iq = kRev ? m - kWord - i : i;
+        uint32_t slot = word_hash(kmer, log2_slots);
+        for (int32_t j; (j = table[slot]) >= 0; slot = (slot + 1) & mask)
+            if (akmer[j] == kmer) {
+                const int b = j - iq + m;
+                atomicAdd(&hist[b >> 1], (b & 1) ? 65536u : 1u);
+            }
+    }
+    __syncthreads();
+    int best_c = 0, best_d = 0;
+    for (int b = 1 + lane; b <= m + n - 1; b += 64) {
+        const int cnt = (int)((hist[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu);
+        if (cnt > 0 && (best_c == 0 || vote_better(cnt, b - m, best_c, best_d))) { best_c = cnt; best_d = b - m; }
+    }
+    for (int sh = 32; sh >= 1; sh >>= 1) {
+        const int oc = __shfl_xor(best_c, sh), od = __shfl_xor(best_d, sh);
+        if (oc > 0 && (best_c == 0 || vote_better(oc, od, best_c, best_d))) { best_c = oc; best_d = od; }
+    }
+    __syncthreads();                           // (every lane has read the histogram before the next pass clears it)
+    *best_c_out = best_c;
+    *best_d_out = best_d;
+}
+
+// anchor_vote_kernel for both strands: one wavefront per query, the same histogram (up to (m + n) / 2 + 1 words) for the forward pass
+// and then for the pass over rc(q).  The query is turned iff rc(q)'s best diagonal has strictly more votes; then the wave rewrites the
+// query's bytes IN PLACE as rc(q) — lane x swaps the pair (x, m - 1 - x) through upper_letter and complement_letter, pairs are disjoint,
+// an odd m's middle letter is complemented where it stands — and every kernel after this one reads the oriented record.  d0 is that of
+// the record as it is left.  flag[q]: kToggle (star.hip's resident parity) ^= turned, else = turned.
+template <bool kToggle>
+__global__ __launch_bounds__(64) void anchor_orient_kernel(uint8_t *__restrict__ bytes, const int64_t *__restrict__ off, int n,
+                                                            const uint32_t *__restrict__ akmer, const int32_t *__restrict__ table, int log2_slots,
+                                                            int32_t *__restrict__ d0_out, uint8_t *__restrict__ flag) {
+    extern __shared__ uint32_t hist[];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    uint8_t *qb = bytes + off[q];
+    const int m = (int)(off[q + 1] - off[q]);
+    int cf, df, cr, dr;
+    orient_pass<false>(hist, qb, m, n, akmer, table, log2_slots, lane, &cf, &df);
+    orient_pass<true>(hist, qb, m, n, akmer, table, log2_slots, lane, &cr, &dr);
+    const bool turn = cr > cf;                 // (uniform over the wave: both reductions leave every lane with the same pair)
+    if (turn) {
+        for (int x = lane; x < m / 2; x += 64) {
+            const uint8_t lo = qb[x], hi = qb[m - 1 - x];
+            qb[x] = complement_letter(upper_letter(hi));
+            qb[m - 1 - x] = complement_letter(upper_letter(lo));
+        }
+        if ((m & 1) && lane == 0) qb[m / 2] = complement_letter(upper_letter(qb[m / 2]));
+    }
+    if (lane == 0) {
+        const int c = turn ? cr : cf, d = turn ? dr : df;
+        d0_out[q] = c > 0 ? d : min(max(0, -m), n);
+        flag[q] = kToggle ? (uint8_t)(flag[q] ^ (turn ? 1 : 0)) : (uint8_t)(turn ? 1 : 0);
+    }
+}
+
+// status bit 3 (MP_ANCHOR_REVERSED) of the records whose flag is set: after the last traceback that writes their meta record
+__global__ __launch_bounds__(256) void anchor_mark_kernel(int32_t *__restrict__ meta, const uint8_t *__restrict__ flag, int nq) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nq && flag[q]) meta[(size_t)q * MP_ANCHOR_META + 7] |= MP_ANCHOR_REVERSED;
 }
 
 // ---- the banded Gotoh sweep ----------------------------------------------------------------------------------------------------------

@@ -49,6 +49,18 @@ __global__ __launch_bounds__(256) void cluster_code_kernel(const uint8_t *__rest
     if (g < total) code[g] = (uint8_t)base_code(bytes[g]);
 }
 
+// Both strands: sequence n + i of the store is rc(i) in codes — reversed, a code below 4 replaced by its complement 3 - code (A, C, G, T
+// are 0 .. 3), every other code kept.  One workgroup per sequence; off holds 2 n + 1 offsets.
+__global__ __launch_bounds__(256) void cluster_revcomp_kernel(uint8_t *__restrict__ code, const int64_t *__restrict__ off, int n) {
+    const int i = blockIdx.x;
+    const int64_t src = off[i], dst = off[n + i];
+    const int m = (int)(off[i + 1] - src);
+    for (int x = threadIdx.x; x < m; x += 256) {
+        const uint8_t cd = code[src + m - 1 - x];
+        code[dst + x] = cd < 4 ? (uint8_t)(3 - cd) : cd;
+    }
+}
+
 // ---- the block index -------------------------------------------------------------------------------------------------------------------
 // Members lie back to back in position space: member k owns positions mpos[k] .. mpos[k + 1).
 __global__ __launch_bounds__(256) void cluster_index_kernel(const uint8_t *__restrict__ code, const int64_t *__restrict__ off,
@@ -358,7 +370,8 @@ struct Run {
         if ((size_t)max_pos > total) max_pos = (int32_t)std::max<size_t>(total, 1);
         table_slots = 16;
         while (table_slots < 2 * (size_t)max_pos) table_slots <<= 1;
-        qbatch = (int32_t)std::min<long long>(std::max<long long>(c->cl_n, 1), 1 << 18);
+        // (the free memory read above is what the store left: with the reverse copies resident the budgets below count the doubled store)
+        qbatch = (int32_t)std::min<long long>(std::max<long long>((c->cl_rev ? 2LL : 1LL) * c->cl_n, 1), 1 << 18);
         ghash_words = std::min<size_t>(std::max<size_t>(free_b / 8 / 4, (size_t)1 << 22), (size_t)1 << 28);
         cand_cap = std::max<size_t>((size_t)1 << 22, (size_t)max_members);
         pbatch = env_cap("MP_CLUSTER_PAIR_BATCH", 1 << 22);
@@ -551,11 +564,52 @@ void reset_stats(mp_ctx *c) {
     for (int64_t &x : c->cl_counts) x = 0;
 }
 
+// The reverse copies, built on the device from the resident codes on the first both-strand call: the store grows to 2 cl_total codes
+// and 2 cl_n + 1 offsets; cl_n and cl_total keep counting the forward half.
+int ensure_reverse(mp_ctx *c, const char *who) {
+    if (c->cl_rev) return MP_OK;
+    const size_t n = (size_t)c->cl_n, total = c->cl_total;
+    HIPCK(c, hipSetDevice(c->dev));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    std::vector<int64_t> off2(2 * n + 1);
+    for (size_t i = 0; i <= n; i++) off2[i] = c->cl_off_host[i];
+    for (size_t i = 1; i <= n; i++) off2[n + i] = (int64_t)total + c->cl_off_host[i];
+    uint8_t *code2 = nullptr;
+    int64_t *d_off2 = nullptr;
+    int rc;
+    if ((rc = dev_alloc(c, &code2, 2 * total)) || (rc = dev_alloc(c, &d_off2, 2 * n + 1))) {
+        dev_free(c, &code2, 2 * total);
+        dev_free(c, &d_off2, 2 * n + 1);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(code2, c->cl_code, total, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off2, off2.data(), sizeof(int64_t) * (2 * n + 1), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cluster_revcomp_kernel, dim3((unsigned)n), dim3(256), 0, c->stream, code2, (const int64_t *)d_off2, (int)n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        dev_free(c, &code2, 2 * total);
+        dev_free(c, &d_off2, 2 * n + 1);
+        return fail(c, MP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    }
+    dev_free(c, &c->cl_code, total);
+    dev_free(c, &c->cl_off, n + 1);
+    c->cl_code = code2;
+    c->cl_off = d_off2;
+    c->cl_off_host.swap(off2);
+    c->cl_rev = true;
+    return MP_OK;
+}
+
 }  // namespace
 
 void free_cluster(mp_ctx *c) {
-    dev_free(c, &c->cl_code, c->cl_total);
-    dev_free(c, &c->cl_off, (size_t)c->cl_n + 1);
+    const size_t k = c->cl_rev ? 2 : 1;
+    dev_free(c, &c->cl_code, k * c->cl_total);
+    dev_free(c, &c->cl_off, k * (size_t)c->cl_n + 1);
+    c->cl_rev = false;
     c->cl_n = 0;
     c->cl_total = 0;
     c->cl_off_host.clear();
@@ -601,15 +655,24 @@ int mp_cluster_load(mp_ctx *c, int32_t n, const uint8_t *bytes, const int64_t *o
     return MP_OK;
 }
 
-int mp_cluster_pairs(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int32_t *r_idx, const mp_cluster_params *p, int32_t *out) {
-    if (!c) return MP_ERR_ARG;
-    if (c->cl_n == 0) return fail(c, MP_ERR_ARG, "mp_cluster_pairs: no sequences (mp_cluster_load first)");
-    if (n_pairs < 0 || !p || (n_pairs && (!q_idx || !r_idx || !out))) return fail(c, MP_ERR_ARG, "mp_cluster_pairs: bad arguments");
+}  // extern "C"
+
+namespace {
+
+// mp_cluster_pairs (q_strand == null) and mp_cluster_pairs_strands: the query of pair x is sequence q_idx[x], or its reverse copy
+// cl_n + q_idx[x] of the store where q_strand[x] is set; anchors are forward copies.
+int pairs_impl(mp_ctx *c, const char *who, int64_t n_pairs, const int32_t *q_idx, const int32_t *r_idx, const int32_t *q_strand,
+               const mp_cluster_params *p, int32_t *out) {
     int rc;
-    if ((rc = check_params(c, "mp_cluster_pairs", p))) return rc;
-    for (int64_t x = 0; x < n_pairs; x++)
+    if ((rc = check_params(c, who, p))) return rc;
+    for (int64_t x = 0; x < n_pairs; x++) {
         if (q_idx[x] < 0 || q_idx[x] >= c->cl_n || r_idx[x] < 0 || r_idx[x] >= c->cl_n)
-            return fail(c, MP_ERR_ARG, "mp_cluster_pairs: pair %lld names sequence %d / %d of %d", (long long)x, q_idx[x], r_idx[x], c->cl_n);
+            return fail(c, MP_ERR_ARG, "%s: pair %lld names sequence %d / %d of %d", who, (long long)x, q_idx[x], r_idx[x], c->cl_n);
+        if (q_strand && (q_strand[x] < 0 || q_strand[x] > 1)) return fail(c, MP_ERR_ARG, "%s: pair %lld names strand %d (0 or 1)", who, (long long)x, q_strand[x]);
+    }
+    if (q_strand && n_pairs && (rc = ensure_reverse(c, who))) return rc;
+    const int32_t n_seq = c->cl_n;
+    auto qseq = [&](int64_t x) { return q_strand && q_strand[x] ? n_seq + q_idx[x] : q_idx[x]; };
     const auto t0 = std::chrono::steady_clock::now();
     reset_stats(c);
     if (n_pairs == 0) return MP_OK;
@@ -621,7 +684,7 @@ int mp_cluster_pairs(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int
     std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return r_idx[a] < r_idx[b]; });
     std::vector<int32_t> anchors;
     for (int64_t x : order) if (anchors.empty() || anchors.back() != r_idx[x]) anchors.push_back(r_idx[x]);
-    std::vector<int32_t> members, queries, lim, q_of((size_t)c->cl_n, -1);
+    std::vector<int32_t> members, queries, lim, q_of((q_strand ? 2 : 1) * (size_t)c->cl_n, -1);
     std::vector<Cand> cands;
     std::vector<PairIn> pin;
     std::vector<PairOut> pout;
@@ -634,7 +697,7 @@ int mp_cluster_pairs(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int
         size_t end = at;
         queries.clear();
         while (end < order.size() && r_idx[order[end]] <= members.back()) {
-            const int32_t q = q_idx[order[end++]];
+            const int32_t q = qseq(order[end++]);
             if (q_of[(size_t)q] < 0) { q_of[(size_t)q] = (int32_t)queries.size(); queries.push_back(q); }
         }
         lim.assign(queries.size(), (int32_t)members.size());
@@ -646,14 +709,14 @@ int mp_cluster_pairs(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int
         for (size_t x = at; x < end; x++) {
             const int64_t pi = order[x];
             const int32_t k = (int32_t)(std::lower_bound(members.begin(), members.end(), r_idx[pi]) - members.begin());
-            const Cand key{q_of[(size_t)q_idx[pi]], k, 0, 0};
+            const Cand key{q_of[(size_t)qseq(pi)], k, 0, 0};
             const auto it = std::lower_bound(cands.begin(), cands.end(), key, [](const Cand &a, const Cand &b) { return a.q != b.q ? a.q < b.q : a.member < b.member; });
             const bool hit = it != cands.end() && it->q == key.q && it->member == k;
             int32_t *o = out + (size_t)pi * MP_CLUSTER_PAIR;
             o[0] = hit ? it->votes : 0;
             o[1] = hit ? it->d0 : 0;
             o[2] = MP_ANCHOR_NO_SCORE; o[3] = 0; o[4] = MP_CLUSTER_NOT_SEEDED | 1;
-            if (o[0] >= p->min_votes) { pin.push_back(PairIn{q_idx[pi], r_idx[pi], o[1], 0}); pin_of.push_back(pi); }
+            if (o[0] >= p->min_votes) { pin.push_back(PairIn{qseq(pi), r_idx[pi], o[1], 0}); pin_of.push_back(pi); }
         }
         if ((rc = run.align(pin, &pout))) return rc;
         for (size_t x = 0; x < pin.size(); x++) {
@@ -668,12 +731,17 @@ int mp_cluster_pairs(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int
     return MP_OK;
 }
 
-int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of, int32_t *rep_of_cluster, int32_t *n_match_of, int32_t *n_clusters) {
-    if (!c) return MP_ERR_ARG;
-    if (c->cl_n == 0) return fail(c, MP_ERR_ARG, "mp_cluster_greedy: no sequences (mp_cluster_load first)");
-    if (!p || !cluster_of || !rep_of_cluster || !n_match_of || !n_clusters) return fail(c, MP_ERR_ARG, "mp_cluster_greedy: null argument");
+// mp_cluster_greedy (strand_of == null) and mp_cluster_greedy_strands.  Both strands: a seeding's query list is the forward copies
+// followed by their reverse copies cl_n + s, so candidate q >= nq is the reverse copy of query q - nq; similar_pairs aligns the
+// forward candidates first and then the reverse candidates of the (query, member) pairs whose forward test did not hold — per
+// representative "forward first, then reverse", and a pair yields at most one join, which carries its strand.  Representatives and
+// indexed members are forward copies throughout.
+int greedy_impl(mp_ctx *c, const char *who, const mp_cluster_params *p, int32_t *cluster_of, int32_t *rep_of_cluster, int32_t *n_match_of,
+                int32_t *strand_of, int32_t *n_clusters) {
     int rc;
-    if ((rc = check_params(c, "mp_cluster_greedy", p))) return rc;
+    if ((rc = check_params(c, who, p))) return rc;
+    const bool both = strand_of != nullptr;
+    if (both && (rc = ensure_reverse(c, who))) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     reset_stats(c);
     Run run(c, *p);
@@ -683,23 +751,53 @@ int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of
     std::iota(rest.begin(), rest.end(), 0);
     std::stable_sort(rest.begin(), rest.end(), [&](int32_t a, int32_t b) { return run.len(a) > run.len(b); });
     for (int32_t i = 0; i < n; i++) cluster_of[i] = -1;
+    if (both) for (int32_t i = 0; i < n; i++) strand_of[i] = 0;
     int32_t nc = 0;
-    struct Join { int32_t q, member, n_match; };
-    std::vector<int32_t> members, reps, queries, lim, best, best_nm;
+    struct Join { int32_t q, member, n_match, strand; };
+    std::vector<int32_t> members, reps, queries, lim, best, best_nm, best_strand;
     std::vector<Cand> cands;
     std::vector<PairIn> pin;
     std::vector<PairOut> pout;
     std::vector<Join> joins;
     std::vector<char> real;
+    std::vector<Cand> rcands;
+    std::vector<uint64_t> held;
+    // queries -> (queries, their reverse copies), lim -> (lim, lim)
+    auto both_strands = [&]() {
+        const size_t nq = queries.size();
+        queries.resize(2 * nq);
+        lim.resize(2 * nq);
+        for (size_t x = 0; x < nq; x++) { queries[nq + x] = n + queries[x]; lim[nq + x] = lim[x]; }
+    };
     auto similar_pairs = [&](const std::vector<int32_t> &anchors, const std::vector<int32_t> &qs) {      // cands -> joins
         if (p->min_votes == 0) run.complete(lim, &cands);
+        const int32_t nq = both ? (int32_t)(qs.size() / 2) : (int32_t)qs.size();
+        if (both) {            // the reverse candidates wait for the forward results
+            rcands.clear();
+            size_t keep = 0;
+            for (const Cand &cd : cands) { if (cd.q >= nq) rcands.push_back(cd); else cands[keep++] = cd; }
+            cands.resize(keep);
+        }
         pin.resize(cands.size());
         for (size_t x = 0; x < cands.size(); x++) pin[x] = PairIn{qs[(size_t)cands[x].q], anchors[(size_t)cands[x].member], cands[x].d0, 0};
         int rc2 = run.align(pin, &pout);
         joins.clear();
         if (rc2) return rc2;
         for (size_t x = 0; x < cands.size(); x++)
-            if (!(pout[x].status & 1)) joins.push_back(Join{cands[x].q, cands[x].member, pout[x].n_match});
+            if (!(pout[x].status & 1)) joins.push_back(Join{cands[x].q, cands[x].member, pout[x].n_match, 0});
+        if (!both) return (int)MP_OK;
+        held.resize(joins.size());
+        for (size_t x = 0; x < joins.size(); x++) held[x] = ((uint64_t)(uint32_t)joins[x].q << 32) | (uint32_t)joins[x].member;
+        std::sort(held.begin(), held.end());
+        size_t keep = 0;
+        for (const Cand &cd : rcands)
+            if (!std::binary_search(held.begin(), held.end(), ((uint64_t)(uint32_t)(cd.q - nq) << 32) | (uint32_t)cd.member)) rcands[keep++] = cd;
+        rcands.resize(keep);
+        pin.resize(rcands.size());
+        for (size_t x = 0; x < rcands.size(); x++) pin[x] = PairIn{qs[(size_t)rcands[x].q], anchors[(size_t)rcands[x].member], rcands[x].d0, 0};
+        if ((rc2 = run.align(pin, &pout))) return rc2;
+        for (size_t x = 0; x < rcands.size(); x++)
+            if (!(pout[x].status & 1)) joins.push_back(Join{rcands[x].q - nq, rcands[x].member, pout[x].n_match, 1});
         return (int)MP_OK;
     };
     while (!rest.empty()) {
@@ -712,6 +810,7 @@ int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of
             queries.assign(members.begin() + 1, members.end());
             lim.resize(nb - 1);
             std::iota(lim.begin(), lim.end(), 1);
+            if (both) both_strands();
             if ((rc = run.index(members)) || (rc = run.seed(queries, lim, p->min_votes, &cands)) || (rc = similar_pairs(members, queries))) return rc;
         }
         // (2) in order: a member is a representative iff no earlier real representative of the block is similar to it
@@ -721,9 +820,9 @@ int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of
         reps.clear();
         size_t jx = 0;
         for (size_t k = 0; k < nb; k++) {
-            int32_t to = -1, nm = 0;
+            int32_t to = -1, nm = 0, strand = 0;
             for (; jx < joins.size() && (size_t)joins[jx].q + 1 == k; jx++)
-                if (to < 0 && real[(size_t)joins[jx].member]) { to = joins[jx].member; nm = joins[jx].n_match; }
+                if (to < 0 && real[(size_t)joins[jx].member]) { to = joins[jx].member; nm = joins[jx].n_match; strand = joins[jx].strand; }
             const int32_t s = members[k];
             if (to < 0) {
                 real[k] = 1;
@@ -734,26 +833,31 @@ int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of
             } else {
                 cluster_of[s] = cluster_of[members[(size_t)to]];
                 n_match_of[s] = nm;
+                if (both) strand_of[s] = strand;
             }
         }
         c->cl_ms[3] += ms_since(t1);
         // (3) every later unassigned sequence against the block's representatives; (4) it joins the smallest-numbered one that passes
         queries.assign(rest.begin() + (long)nb, rest.end());
         if (!queries.empty()) {
-            lim.assign(queries.size(), (int32_t)reps.size());
+            const size_t nq = queries.size();
+            lim.assign(nq, (int32_t)reps.size());
+            if (both) both_strands();
             cands.clear();
             if ((rc = run.index(reps)) || (rc = run.seed(queries, lim, p->min_votes, &cands)) || (rc = similar_pairs(reps, queries))) return rc;
             t1 = std::chrono::steady_clock::now();
-            best.assign(queries.size(), -1);
-            best_nm.assign(queries.size(), 0);
+            best.assign(nq, -1);
+            best_nm.assign(nq, 0);
+            best_strand.assign(nq, 0);
             for (const Join &j : joins)
-                if (best[(size_t)j.q] < 0 || j.member < best[(size_t)j.q]) { best[(size_t)j.q] = j.member; best_nm[(size_t)j.q] = j.n_match; }
+                if (best[(size_t)j.q] < 0 || j.member < best[(size_t)j.q]) { best[(size_t)j.q] = j.member; best_nm[(size_t)j.q] = j.n_match; best_strand[(size_t)j.q] = j.strand; }
             rest.clear();
-            for (size_t x = 0; x < queries.size(); x++) {
+            for (size_t x = 0; x < nq; x++) {
                 const int32_t s = queries[x];
                 if (best[x] < 0) { rest.push_back(s); continue; }
                 cluster_of[s] = cluster_of[reps[(size_t)best[x]]];
                 n_match_of[s] = best_nm[x];
+                if (both) strand_of[s] = best_strand[x];
             }
             c->cl_ms[3] += ms_since(t1);
         } else rest.clear();
@@ -762,6 +866,40 @@ int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of
     *n_clusters = nc;
     c->cl_ms[4] = ms_since(t0);
     return MP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mp_cluster_pairs(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int32_t *r_idx, const mp_cluster_params *p, int32_t *out) {
+    if (!c) return MP_ERR_ARG;
+    if (c->cl_n == 0) return fail(c, MP_ERR_ARG, "mp_cluster_pairs: no sequences (mp_cluster_load first)");
+    if (n_pairs < 0 || !p || (n_pairs && (!q_idx || !r_idx || !out))) return fail(c, MP_ERR_ARG, "mp_cluster_pairs: bad arguments");
+    return pairs_impl(c, "mp_cluster_pairs", n_pairs, q_idx, r_idx, nullptr, p, out);
+}
+
+int mp_cluster_pairs_strands(mp_ctx *c, int64_t n_pairs, const int32_t *q_idx, const int32_t *r_idx, const int32_t *q_strand, const mp_cluster_params *p,
+                             int32_t *out) {
+    if (!c) return MP_ERR_ARG;
+    if (c->cl_n == 0) return fail(c, MP_ERR_ARG, "mp_cluster_pairs_strands: no sequences (mp_cluster_load first)");
+    if (n_pairs < 0 || !p || (n_pairs && (!q_idx || !r_idx || !q_strand || !out))) return fail(c, MP_ERR_ARG, "mp_cluster_pairs_strands: bad arguments");
+    return pairs_impl(c, "mp_cluster_pairs_strands", n_pairs, q_idx, r_idx, q_strand, p, out);
+}
+
+int mp_cluster_greedy(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of, int32_t *rep_of_cluster, int32_t *n_match_of, int32_t *n_clusters) {
+    if (!c) return MP_ERR_ARG;
+    if (c->cl_n == 0) return fail(c, MP_ERR_ARG, "mp_cluster_greedy: no sequences (mp_cluster_load first)");
+    if (!p || !cluster_of || !rep_of_cluster || !n_match_of || !n_clusters) return fail(c, MP_ERR_ARG, "mp_cluster_greedy: null argument");
+    return greedy_impl(c, "mp_cluster_greedy", p, cluster_of, rep_of_cluster, n_match_of, nullptr, n_clusters);
+}
+
+int mp_cluster_greedy_strands(mp_ctx *c, const mp_cluster_params *p, int32_t *cluster_of, int32_t *rep_of_cluster, int32_t *n_match_of, int32_t *strand_of,
+                              int32_t *n_clusters) {
+    if (!c) return MP_ERR_ARG;
+    if (c->cl_n == 0) return fail(c, MP_ERR_ARG, "mp_cluster_greedy_strands: no sequences (mp_cluster_load first)");
+    if (!p || !cluster_of || !rep_of_cluster || !n_match_of || !strand_of || !n_clusters) return fail(c, MP_ERR_ARG, "mp_cluster_greedy_strands: null argument");
+    return greedy_impl(c, "mp_cluster_greedy_strands", p, cluster_of, rep_of_cluster, n_match_of, strand_of, n_clusters);
 }
 
 int mp_cluster_stats(mp_ctx *c, double *ms, int64_t *counts) {

@@ -294,6 +294,7 @@ struct mp_ctx {
     int32_t an_par[6] = {0, 0, 0, 0, 0, 0};  // mp_anchor_params
     double an_ms[5] = {0, 0, 0, 0, 0};
     int64_t an_counts[3] = {0, 0, 0};
+    int32_t an_both = 0;                     // mp_anchor_strands: mp_anchor_align and mp_star_round vote both strands and turn a query once
     // clustering by identity (cluster.hip, include/mprime_cluster.h): the sequences of mp_cluster_load and the times / counts of the last call
     uint8_t *cl_code = nullptr;              // [cl_total] 0..3 = A, C, G, T, 4 = anything else, sequences back to back
     int64_t *cl_off = nullptr;               // [cl_n + 1]
@@ -302,6 +303,7 @@ struct mp_ctx {
     std::vector<int64_t> cl_off_host;
     double cl_ms[5] = {0, 0, 0, 0, 0};
     int64_t cl_counts[3] = {0, 0, 0};
+    bool cl_rev = false;                     // the store holds the reverse complements too: sequence cl_n + i = rc(i), 2 cl_n + 1 offsets
     // merging by identity (ani.hip, include/mprime_ani.h): the sketches of mp_ani_sketch, TAB, and the times / counts since
     uint32_t *ani_sk = nullptr;              // [ani_n][ani_s] ascending, 0xFFFFFFFF past a sketch's size
     int32_t *ani_sizes = nullptr;            // [ani_n]
@@ -315,6 +317,7 @@ struct mp_ctx {
     int32_t st_n = 0;
     size_t st_total = 0;
     std::vector<int64_t> st_off_host;
+    uint8_t *st_parity = nullptr;            // [st_n] 1: st_bytes holds the reverse complement of the loaded record (both-strand rounds)
     int32_t st_an = 0, st_stride = 0, st_width = 0;      // of the last round: anchor positions, slots per record of the path store (padded), L'
     int32_t *st_d0 = nullptr, *st_end = nullptr, *st_meta = nullptr, *st_wfin = nullptr;     // [st_n] / [2 st_n] / [st_n][MP_ANCHOR_META] / [st_n]
     uint8_t *st_arow = nullptr;              // [st_n][st_an] the aligned letters in anchor space

@@ -245,6 +245,7 @@ void free_star(mp_ctx *c) {
     free_round(c);
     dev_free(c, &c->st_bytes, c->st_total);
     dev_free(c, &c->st_off, (size_t)c->st_n + 1);
+    dev_free(c, &c->st_parity, (size_t)c->st_n);
     c->st_n = 0;
     c->st_total = 0;
     c->st_off_host.clear();
@@ -271,8 +272,10 @@ int mp_star_load(mp_ctx *c, int32_t n, const uint8_t *bytes, const int64_t *off)
     c->st_off_host.resize((size_t)n + 1);
     for (int32_t q = 0; q <= n; q++) c->st_off_host[(size_t)q] = off[q] - off[0];
     int rc;
-    if ((rc = dev_alloc(c, &c->st_bytes, c->st_total)) || (rc = dev_alloc(c, &c->st_off, (size_t)n + 1))) { free_star(c); return rc; }
+    if ((rc = dev_alloc(c, &c->st_bytes, c->st_total)) || (rc = dev_alloc(c, &c->st_off, (size_t)n + 1)) ||
+        (rc = dev_alloc(c, &c->st_parity, (size_t)n))) { free_star(c); return rc; }
     hipError_t e = hipMemcpyAsync(c->st_bytes, bytes + off[0], c->st_total, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->st_parity, 0, (size_t)n, c->stream);        // every record is held as given
     if (e == hipSuccess) e = hipMemcpyAsync(c->st_off, c->st_off_host.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { free_star(c); return fail(c, MP_ERR_DEVICE, "mp_star_load: %s", hipGetErrorString(e)); }
@@ -357,9 +360,11 @@ int mp_star_round(mp_ctx *c, const uint8_t *anchor, int32_t n, const mp_anchor_p
     };
     auto launched = [&]() { if (e == hipSuccess) e = hipGetLastError(); return e == hipSuccess; };
     auto dev_fail = [&]() { return finish(fail(c, MP_ERR_DEVICE, "mp_star_round: %s", hipGetErrorString(e))); };
+    const bool both = c->an_both != 0;
     const size_t vote_lds = ((size_t)(max_m + n) / 2 + 1) * sizeof(uint32_t);
     if (vote_lds > 65536) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(anchor_vote_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vote_lds);
+        e = hipFuncSetAttribute(both ? reinterpret_cast<const void *>(anchor_orient_kernel<true>) : reinterpret_cast<const void *>(anchor_vote_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vote_lds);
         if (e != hipSuccess) return dev_fail();
     }
     const int npad = (n + 15) & ~15, mstride = (max_m + 15) & ~15;
@@ -401,8 +406,12 @@ int mp_star_round(mp_ctx *c, const uint8_t *anchor, int32_t n, const mp_anchor_p
         if ((rc = fill_segments(c, &seg, 1))) return finish(rc);
     }
     if (!mark(-1)) return dev_fail();
-    hipLaunchKernelGGL(anchor_vote_kernel, dim3((unsigned)N), dim3(64), vote_lds, c->stream, (const uint8_t *)c->st_bytes, (const int64_t *)c->st_off, n,
-                       (const uint32_t *)c->an_kmer, (const int32_t *)c->an_table, log2_slots, c->st_d0);
+    if (both)              // a turned record stays turned in the resident bytes; st_parity is its orientation against the loaded record
+        hipLaunchKernelGGL(anchor_orient_kernel<true>, dim3((unsigned)N), dim3(64), vote_lds, c->stream, c->st_bytes, (const int64_t *)c->st_off, n,
+                           (const uint32_t *)c->an_kmer, (const int32_t *)c->an_table, log2_slots, c->st_d0, c->st_parity);
+    else
+        hipLaunchKernelGGL(anchor_vote_kernel, dim3((unsigned)N), dim3(64), vote_lds, c->stream, (const uint8_t *)c->st_bytes, (const int64_t *)c->st_off, n,
+                           (const uint32_t *)c->an_kmer, (const int32_t *)c->an_table, log2_slots, c->st_d0);
     if (!launched() || !mark(0)) return dev_fail();
     std::vector<int64_t> h_tboff;
     for (size_t b = 0; b + 1 < bstart.size(); b++) {
@@ -451,6 +460,10 @@ int mp_star_round(mp_ctx *c, const uint8_t *anchor, int32_t n, const mp_anchor_p
     }
     // the insertion profile, the columns, the rows, the counts
     if (!mark(-1)) return dev_fail();
+    if (both) {            // (after the last traceback: an escalated record's meta record was written again)
+        hipLaunchKernelGGL(anchor_mark_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, c->st_meta, (const uint8_t *)c->st_parity, N);
+        if (!launched()) return dev_fail();
+    }
     hipLaunchKernelGGL(star_profile_kernel, dim3((unsigned)((N + kProfileRows - 1) / kProfileRows), (unsigned)((S / 8 + 255) / 256)), dim3(256), 0, c->stream,
                        (const uint16_t *)c->st_runlen, (const int32_t *)c->st_meta, N, S, c->st_ins);
     if (!launched()) return dev_fail();

@@ -8,6 +8,9 @@ writes OUT (the placed records in input order, one line of L' letters each), OUT
 per round) and OUT.unaligned.fa (the unplaced records as given).  Records are those of the FASTA front end every drop-in uses
 (msa.read_records): an id is the header's first token, '>' included.  The round loop lives here: round 0's anchor is the longest
 record, every later one the majority consensus of the round before, computed from the column counts the device hands back.
+`--adjust-direction` (mafft's --adjustdirection): every round votes both strands of a record and turns it where its reverse complement
+seeds better; a turned record is written under the id `_R_<id>`, its row is that of the reverse complement, and OUT.star.tsv gets a last
+column `strand`.  OUT.unaligned.fa keeps records as given.
 """
 from __future__ import annotations
 
@@ -17,11 +20,16 @@ import time
 
 import numpy as np
 
-from ._abi import ANCHOR_MAX_BAND, ANCHOR_MAX_LEN, ANCHOR_MAX_PARAM, STAR_MAX_ROUNDS, Library
+from ._abi import ANCHOR_MAX_BAND, ANCHOR_MAX_LEN, ANCHOR_MAX_PARAM, ANCHOR_REVERSED, STAR_MAX_ROUNDS, Library
 
 META_FIELDS = ("score", "d0", "n_match", "n_ins", "n_del", "first_col", "last_col", "status", "first_anchor", "last_anchor", "band")
 _UPPER = np.arange(256, dtype=np.uint8)
 _UPPER[ord("a"):ord("z") + 1] -= 32
+
+
+def oriented_id(ident: str, reversed_: bool) -> str:
+    """mafft's name of a record it turned: `>_R_<id>`."""
+    return (">_R_" + ident[1:] if ident.startswith(">") else "_R_" + ident) if reversed_ else ident
 
 
 def anchor_of_counts(counts, placed):
@@ -36,8 +44,9 @@ def anchor_of_counts(counts, placed):
 
 class StarAlignment:
     def __init__(self, infile, outfile, rounds=2, band=32, match=5, mismatch=4, gap_open=10, gap_extend=2, min_identity=0.5, device=0,
-                 library=None):
+                 library=None, adjust_direction=False):
         self.infile, self.outfile = infile, outfile
+        self.adjust_direction = bool(adjust_direction)
         self.rounds, self.band = int(rounds), int(band)
         self.match, self.mismatch, self.gap_open, self.gap_extend = int(match), int(mismatch), int(gap_open), int(gap_extend)
         self.min_identity_permille = int(round(float(min_identity) * 1000))
@@ -78,6 +87,8 @@ class StarAlignment:
             raise RuntimeError(f"{lib.path} has no star alignment (include/mprime_star.h): there is no host fallback")
         ctx = lib.context(self.device)
         try:
+            if self.adjust_direction:
+                ctx.anchor_strands(True)
             ctx.star_load(self.data, self.off)
             anchor = _UPPER[self.data[self.off[self.centre]:self.off[self.centre + 1]]].tobytes()
             self._anchors, self.round_stats = [], []
@@ -111,13 +122,15 @@ class StarAlignment:
             for q0 in range(0, len(ok), 1 << 16):
                 parts = []
                 for q in np.flatnonzero(ok[q0:q0 + (1 << 16)]) + q0:
-                    parts.append(self._ids[q].encode())
+                    parts.append(oriented_id(self._ids[q], bool(self._meta[q, 7] & ANCHOR_REVERSED)).encode())
                     parts.append(self._rows[q].tobytes())
                 if parts:
                     fo.write(b"\n".join(parts) + b"\n")
         with open(self.outfile + ".star.tsv", "w") as fo:
-            fo.write("id\tstatus\tband\tscore\td0\tn_match\tn_ins\tn_del\n")
-            fo.writelines("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(self._ids[q], mt[7], mt[10], mt[0], mt[1], mt[2], mt[3], mt[4])
+            strand = self.adjust_direction
+            fo.write("id\tstatus\tband\tscore\td0\tn_match\tn_ins\tn_del" + ("\tstrand\n" if strand else "\n"))
+            fo.writelines("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}{}\n".format(self._ids[q], mt[7], mt[10], mt[0], mt[1], mt[2], mt[3], mt[4],
+                                                                      ("\t-" if mt[7] & ANCHOR_REVERSED else "\t+") if strand else "")
                           for q, mt in enumerate(self._meta.tolist()))
             for k, st in enumerate(self.round_stats):
                 fo.write("# round {}: n {} width {} placed {} band_warnings {}\n".format(k, st["n"], st["width"], st["placed"], st["band_warnings"]))
@@ -180,6 +193,8 @@ def parse_args(argv=None):
     p.add_argument("--gap-extend", type=int, default=2, metavar="<int>")
     p.add_argument("--min-identity", type=float, default=0.5, metavar="<float>",
                    help="a record with fewer matching pairs than this share of its length goes to <out>.unaligned.fa. Default: 0.5")
+    p.add_argument("--adjust-direction", action="store_true", help="turn a record whose reverse complement seeds better (mafft --adjustdirection); "
+                   "it is written as _R_<id>. Default: records are aligned as given")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal (default 0)")
     args = p.parse_args(argv)
     if not 1 <= args.rounds <= STAR_MAX_ROUNDS:
@@ -200,7 +215,8 @@ def main(argv=None):
     e1 = time.time()
     args = parse_args(argv)                     # exit status 2 on bad flags
     app = StarAlignment(args.input, args.out, rounds=args.rounds, band=args.band, match=args.match, mismatch=args.mismatch,
-                        gap_open=args.gap_open, gap_extend=args.gap_extend, min_identity=args.min_identity, device=args.device)
+                        gap_open=args.gap_open, gap_extend=args.gap_extend, min_identity=args.min_identity, device=args.device,
+                        adjust_direction=args.adjust_direction)
     try:
         app.run()                               # SystemExit with a message (status 1) on an unreadable or empty input
     except ValueError as e:
