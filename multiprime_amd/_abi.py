@@ -199,6 +199,15 @@ DEGE_SORT_MIN = 64                  # MP_DEGE_SORT_MIN: the sort sizes are the p
 DEGE_MERGE_LDS = 4096               # MP_DEGE_MERGE_LDS: more unique mers in a window are merged from global memory
 DEGE_WIN = 4                        # MP_DEGE_WIN
 DEGE_REC = 35                       # MP_DEGE_REC
+# include/mprime_ont.h: read ends against expanded primers on the device (csrc/ont.hip) — exported by libmprime_hip.so only; the checker of
+# these calls is difflib itself beside the plain restatement of the rule in tests/ont_ref.py
+ONT_SYMBOLS = [
+    ("mp_ont_set_keys", C.c_int, [_p, C.c_int32, _p, _p]),
+    ("mp_ont_assign", C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
+    ("mp_ont_stats", C.c_int, [_p, _p, _p]),
+]
+ONT_MAX_LEN = 64                    # MP_ONT_MAX_LEN
+ONT_Q_ROWS, ONT_Q_COLS = 129, 65    # MP_ONT_Q_ROWS, MP_ONT_Q_COLS
 
 
 def prefer_staged_copies():
@@ -310,10 +319,14 @@ class Library:
         self.dege = all(hasattr(self.dll, name) for name, _, _ in DEGE_SYMBOLS)
         if self.backend == "hip" and not self.dege:
             raise MprimeError(-2, f"{path} lacks the DegePrime entry points of include/mprime_dege.h: rebuild it")
+        self.ont = all(hasattr(self.dll, name) for name, _, _ in ONT_SYMBOLS)
+        if self.backend == "hip" and not self.ont:
+            raise MprimeError(-2, f"{path} lacks the read-assignment entry points of include/mprime_ont.h: rebuild it")
         for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
                                 (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else []) +
-                                (DEGE_SYMBOLS if self.dege else []) + (STRAND_SYMBOLS if self.strands else [])):
+                                (DEGE_SYMBOLS if self.dege else []) + (ONT_SYMBOLS if self.ont else []) +
+                                (STRAND_SYMBOLS if self.strands else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -1161,6 +1174,43 @@ class Context:
         ms, counts = np.zeros(2, np.float64), np.zeros(4, np.int64)
         self._ck(self.d.mp_dege_stats(self.h, _ptr(ms), _ptr(counts)))
         return dict(zip(("window_ms", "merge_ms"), ms.tolist())), dict(zip(("windows", "printed", "unique", "global_windows"), counts.tolist()))
+
+    # include/mprime_ont.h
+    def _need_ont(self):
+        if not self.lib.ont:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_ont.h (libmprime_hip.so does)")
+
+    def ont_set_keys(self, data, off):
+        """Make the keys data[off[i]:off[i+1]] (upper-case A, C, G, T, at most ONT_MAX_LEN bytes each) resident (mp_ont_set_keys)."""
+        self._need_ont()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        self._ck(self.d.mp_ont_set_keys(self.h, len(off) - 1, _ptr(data), _ptr(off)))
+
+    def ont_assign(self, data, off, q):
+        """(key int32 [n], m int32 [n]): per piece data[off[p]:off[p+1]] the resident key of the highest rank q[T][M], the first among
+        equals, and its match count (mp_ont_assign).  q: int32 [ONT_Q_ROWS][ONT_Q_COLS]."""
+        self._need_ont()
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        q = np.ascontiguousarray(q, dtype=np.int32)
+        if q.shape != (ONT_Q_ROWS, ONT_Q_COLS):
+            raise ValueError(f"ont_assign: q must be {ONT_Q_ROWS} x {ONT_Q_COLS}")
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        n = len(off) - 1
+        key, m = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self._ck(self.d.mp_ont_assign(self.h, n, _ptr(data), _ptr(off), _ptr(q), _ptr(key), _ptr(m)))
+        return key[:n], m[:n]
+
+    def ont_stats(self):
+        """({assign_ms}, {keys, pieces}): device event time of the assignment kernels and the counts since the last ont_set_keys."""
+        self._need_ont()
+        ms, counts = np.zeros(1, np.float64), np.zeros(2, np.int64)
+        self._ck(self.d.mp_ont_stats(self.h, _ptr(ms), _ptr(counts)))
+        return {"assign_ms": float(ms[0])}, dict(zip(("keys", "pieces"), counts.tolist()))
 
     def device_bytes(self) -> int:
         b = C.c_int64(0)

@@ -312,6 +312,7 @@ void mp_destroy(mp_ctx *c) {
     free_star(c);
     free_ani(c);
     free_dege(c);
+    free_ont(c);
     // The library's own streams go AFTER the stages: free_eval() waits for the second stream before it releases what launches on it read.
     // [r6] They went first, so that wait named a destroyed stream (freed memory of the runtime).  Found by reading while hunting two of 57
     // `bench.py` runs that died inside the runtime (std::bad_variant_access / SIGSEGV); 3000 contexts in either order did not reproduce a

@@ -330,6 +330,12 @@ struct mp_ctx {
     int64_t st_counts[6] = {0, 0, 0, 0, 0, 0};
     // DegePrime's oligomers per window (dege.hip, include/mprime_dege.h): the alignment, the windows and the result of the merging
     mp::DegeState *dege = nullptr;
+    // nanopore reads to primers (ont.hip, include/mprime_ont.h): the resident key list of mp_ont_set_keys, and the times / counts since
+    uint64_t *ont_keys = nullptr;            // [ont_n][5]: position masks A, C, G, T and length | counts (ont.hip: OntKey)
+    int32_t *ont_q = nullptr;                // [MP_ONT_Q_ROWS][MP_ONT_Q_COLS], uploaded per mp_ont_assign
+    int32_t ont_n = 0, ont_max_len = 0;      // keys resident, the longest of them
+    double ont_ms = 0;
+    int64_t ont_counts[2] = {0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run
@@ -443,6 +449,7 @@ void free_cluster(mp_ctx *c);    // cluster.hip
 void free_star(mp_ctx *c);       // star.hip
 void free_ani(mp_ctx *c);        // ani.hip
 void free_dege(mp_ctx *c);       // dege.hip
+void free_ont(mp_ctx *c);        // ont.hip
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

@@ -215,5 +215,12 @@ dege)            # profiles/dege.txt: DegePrime on the recorded 150 x 320 slice 
   timeout -k 10 600 python tools/dege_bench.py 2>&1 | tee $O/dege.txt &&
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof/trace -o t -- python tools/dege_bench.py > /dev/null 2>&1 &&
   python tools/summarize_profile.py $O/prof 2>/dev/null | head -14 | tee -a $O/dege.txt ;;
+ont)             # profiles/ont.txt: reads to primers on a synthetic run (200000 reads, 96 primers, about 1000 keys): device ms from mp_ont_stats, run() wall, a one-core difflib loop over 200 reads scaled linearly; then the same run without the pruning bound and on 64-bit masks
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_ont_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 600 python tools/ont_bench.py 2>&1 | tee $O/ont.txt &&
+  (echo "# MP_ONT_PRUNE=0"; MP_ONT_PRUNE=0 timeout -k 10 600 python tools/ont_bench.py --sample 20) 2>&1 | tee -a $O/ont.txt &&
+  (echo "# MP_ONT_WORD=64"; MP_ONT_WORD=64 timeout -k 10 600 python tools/ont_bench.py --sample 20) 2>&1 | tee -a $O/ont.txt ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
