@@ -9,7 +9,7 @@
  * THE RULE
  *
  * Words and hash.  Letters are upper-cased (base_code of csrc/seedword.hpp).  A word is 12 consecutive letters, all in A/C/G/T; its
- * value is the 24-bit number with the first letter most significant (A = 0, C = 1, G = 2, T = 3), as word_at of csrc/cluster.hip
+ * value is the 24-bit number with the first letter most significant (A = 0, C = 1, G = 2, T = 3), as seed_word of csrc/seedword.hpp
  * builds it.  Its hash is murmur3's 32-bit finaliser of that value:
  *     h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16        (mod 2^32)
  * The finaliser is a bijection, so distinct words have distinct hashes.  (0xFFFFFFFF is the hash of 0x331DA083, which is no 24-bit

@@ -1,5 +1,6 @@
 // anchor.hip — anchored alignment (include/mprime_anchor.h): every query is placed on the anchor of a seed alignment by a banded
-// affine-gap (Gotoh) alignment around a voted seed diagonal.  The vote, sweep and traceback kernels are those of anchorcore.hpp; here:
+// affine-gap (Gotoh) alignment around a voted seed diagonal.  The vote, sweep and traceback kernels are those of anchorcore.hpp (the sweep's
+// rule itself: bandsweep.hpp; the 12-mer of a position, here for the anchor's table: seedword.hpp); here:
 //   anchor_emit_kernel   expands anchor space to the seed's L columns: 16 row bytes per lane, one 128-bit store each
 #include "anchorcore.hpp"
 
@@ -77,12 +78,7 @@ int mp_anchor_set(mp_ctx *c, const uint8_t *codes, int32_t n, const int32_t *col
     std::vector<uint8_t> code((size_t)n);
     for (int32_t j = 0; j < n; j++) code[(size_t)j] = (uint8_t)base_code(codes[j]);
     std::vector<uint32_t> kmer((size_t)n, kEmpty);
-    for (int32_t j = 0; j + kWord <= n; j++) {
-        uint32_t w = 0;
-        bool ok = true;
-        for (int x = 0; x < kWord; x++) { ok = ok && code[(size_t)(j + x)] < 4; w = (w << 2) | (code[(size_t)(j + x)] & 3u); }
-        if (ok) kmer[(size_t)j] = w;
-    }
+    for (int32_t j = 0; j + kWord <= n; j++) kmer[(size_t)j] = seed_word_codes(code.data() + j);
     int log2_slots = 4;
     while ((1 << log2_slots) < 2 * n) log2_slots++;
     const int32_t slots = 1 << log2_slots;
@@ -121,7 +117,7 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
     for (int64_t &x : c->an_counts) x = 0;
     if (nq == 0) return MP_OK;
     const int n = c->an_n, L = c->an_L, W = c->an_par[4], B = 2 * W + 1;
-    const int R = anchor_lane_diagonals(W), Bpad = 64 * R;
+    const int R = lane_diagonals(W), Bpad = 64 * R;
     for (int32_t q = 0; q < nq; q++) {
         const int64_t m = off[q + 1] - off[q];
         if (m < 1 || m > MP_ANCHOR_MAX_LEN) return fail(c, MP_ERR_ARG, "mp_anchor_align: query %d has %lld bases (1..%d)", q, (long long)m, MP_ANCHOR_MAX_LEN);
@@ -217,13 +213,12 @@ int mp_anchor_align(mp_ctx *c, int32_t nq, const uint8_t *bytes, const int64_t *
         if ((e = hipGetLastError()) != hipSuccess) break;
         if ((e = hipEventRecord(ev[1], c->stream)) != hipSuccess) break;
         const dim3 grid((unsigned)((nb + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
-#define MP_ANCHOR_DP(RR)                                                                                                                         \
-        hipLaunchKernelGGL((anchor_dp_kernel<RR, false>), grid, block, dp_lds, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off, (int)nb,        \
-                           (const int32_t *)d_d0, (const uint8_t *)c->an_code, n, W, (int)c->an_par[0], (int)c->an_par[1],                          \
-                           (int)(c->an_par[2] + c->an_par[3]), (int)c->an_par[3], mstride, d_tb, (const int64_t *)d_tboff, d_end,     \
-                           (const int32_t *)nullptr, 0LL)
-        if (R == 1) MP_ANCHOR_DP(1); else if (R == 2) MP_ANCHOR_DP(2); else if (R == 4) MP_ANCHOR_DP(4); else MP_ANCHOR_DP(8);
-#undef MP_ANCHOR_DP
+        for_lane_diagonals(W, [&](auto r) {
+            hipLaunchKernelGGL((anchor_dp_kernel<decltype(r)::value, false>), grid, block, dp_lds, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off,
+                               (int)nb, (const int32_t *)d_d0, (const uint8_t *)c->an_code, n, W, (int)c->an_par[0], (int)c->an_par[1],
+                               (int)(c->an_par[2] + c->an_par[3]), (int)c->an_par[3], mstride, d_tb, (const int64_t *)d_tboff, d_end,
+                               (const int32_t *)nullptr, 0LL);
+        });
         if ((e = hipGetLastError()) != hipSuccess) break;
         if ((e = hipEventRecord(ev[2], c->stream)) != hipSuccess) break;
         hipLaunchKernelGGL((anchor_trace_kernel<false, false>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)d_bytes, (const int64_t *)d_off,

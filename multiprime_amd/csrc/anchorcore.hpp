@@ -1,35 +1,25 @@
 // anchorcore.hpp — the device side of the anchored-alignment rule (include/mprime_anchor.h), shared by anchor.hip (one pass onto a seed's
 // columns) and star.hip (rounds onto a re-estimated anchor, inserted bases kept).  Three kernels per batch of queries:
-//   anchor_vote_kernel   one wavefront per query: its 12-mers are looked up in the anchor's open-addressing table, the votes per
-//                        diagonal counted in an LDS histogram (two 16-bit counters per word), d0 chosen by a wave reduction
-//   anchor_orient_kernel its both-strand form (mp_anchor_strands): the same histogram for q and then for rc(q), the query's bytes
-//                        rewritten in place as rc(q) where that seeds better; anchor_mark_kernel sets status bit 3 afterwards
-//   anchor_dp_kernel     one wavefront per query, lanes own the band's diagonals (R = 1, 2, 4 or 8 neighbouring diagonals per lane for
-//                        2W + 1 <= 64 R).  ANTI-DIAGONAL sweep: at step s the cells with i + j = s are computed; cell (i, j) on diagonal
-//                        d reads its left cell (i, j-1) from diagonal d - 1 and its upper cell (i-1, j) from diagonal d + 1, both
-//                        computed at step s - 1, and its diagonal cell from its own registers — no dependency inside a step, so no
-//                        scan; a lane is busy every other step.  Four predecessor bits per cell (H source 2, E opened, F opened)
-//                        are collected eight rows to a word per diagonal and stored to the traceback buffer in HBM.  Anchor codes
-//                        (shared by the workgroup's waves) and the wave's query codes sit in LDS; the pair score is two compares on
-//                        the codes, so no per-letter profile rows are kept.
+//   anchor_vote_kernel   one wavefront per query: its 12-mers (seedword.hpp) are looked up in the anchor's open-addressing table, the
+//                        votes per diagonal counted in an LDS histogram (two 16-bit counters per word), d0 chosen by a wave reduction
+//                        — one call of vote_pass, the only body of the histogram vote
+//   anchor_orient_kernel its both-strand form (mp_anchor_strands): vote_pass over the same histogram for q and then for rc(q), the
+//                        query's bytes rewritten in place as rc(q) where that seeds better; anchor_mark_kernel sets status bit 3 afterwards
+//   anchor_dp_kernel     one wavefront per query: band_sweep (bandsweep.hpp: the recurrence, its comparison order and the end cell) with
+//                        the TRACE payload — four predecessor bits per cell (H source 2, E opened, F opened) are collected eight rows
+//                        to a word per diagonal and stored to the traceback buffer in HBM.  Anchor codes (shared by the workgroup's
+//                        waves) and the wave's query codes sit in LDS, so no per-letter profile rows are kept.
 //   anchor_trace_kernel  one lane per query walks the bits from the end cell (a chain of dependent loads: latency-bound, so it
 //                        gets its parallelism from the number of queries), writes the letters in anchor space, the meta record and the ops
 // Everything sits in an unnamed namespace: each translation unit that includes this compiles the kernels it instantiates.
 #pragma once
 
-#include "common.hpp"
+#include "bandsweep.hpp"
 #include "seedword.hpp"
-#include "../../include/mprime_anchor.h"
 
 namespace mp {
 
 namespace {
-
-constexpr int kNeg = -(1 << 30);               // "no such cell": below every real score by more than any real score can gain
-constexpr int kNoPath = -(3 << 28);            // a best end score below this was never fed by row 0 (mprime_anchor.h: MP_ANCHOR_MAX_PARAM)
-constexpr int kWord = MP_ANCHOR_WORD;
-
-__host__ __device__ inline uint8_t upper_letter(uint8_t ch) { return ch >= 'a' && ch <= 'z' ? (uint8_t)(ch - 32) : ch; }
 
 // ---- votes --------------------------------------------------------------------------------------------------------------------------
 // better(a, b): diagonal vote (ca, da) beats (cb, db) — more votes, then the smaller |d|, then the smaller d
@@ -40,76 +30,20 @@ __device__ inline bool vote_better(int ca, int da, int cb, int db) {
     return da < db;
 }
 
-__global__ __launch_bounds__(64) void anchor_vote_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict__ off, int n,
-                                                          const uint32_t *__restrict__ akmer, const int32_t *__restrict__ table, int log2_slots,
-                                                          int32_t *__restrict__ d0_out) {
-    extern __shared__ uint32_t hist[];         // bin b = d + m (1 .. m + n - 1): counter (b & 1) of word b >> 1
-    const int q = blockIdx.x, lane = threadIdx.x;
-    const uint8_t *qb = bytes + off[q];
-    const int m = (int)(off[q + 1] - off[q]);
-    const int words = (m + n) / 2 + 1;
-    for (int x = lane; x < words; x += 64) hist[x] = 0;
-    __syncthreads();
-    const uint32_t mask = (1u << log2_slots) - 1;
-    for (int i = lane; i + kWord <= m && n >= kWord; i += 64) {
-        uint32_t kmer = 0;
-        bool ok = true;
-        for (int x = 0; x < kWord; x++) {
-            const int cd = base_code(qb[i + x]);
-            ok = ok && cd < 4;
-            kmer = (kmer << 2) | (uint32_t)(cd & 3);
-        }
-        if (!ok) continue;
-        uint32_t slot = word_hash(kmer, log2_slots);
-        for (int32_t j; (j = table[slot]) >= 0; slot = (slot + 1) & mask)
-            if (akmer[j] == kmer) {
-                const int b = j - i + m;
-                atomicAdd(&hist[b >> 1], (b & 1) ? 65536u : 1u);
-            }
-    }
-    __syncthreads();
-    int best_c = 0, best_d = 0;
-    for (int b = 1 + lane; b <= m + n - 1; b += 64) {
-        const int cnt = (int)((hist[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu);
-        if (cnt > 0 && (best_c == 0 || vote_better(cnt, b - m, best_c, best_d))) { best_c = cnt; best_d = b - m; }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const int oc = __shfl_xor(best_c, sh), od = __shfl_xor(best_d, sh);
-        if (oc > 0 && (best_c == 0 || vote_better(oc, od, best_c, best_d))) { best_c = oc; best_d = od; }
-    }
-    if (lane == 0) d0_out[q] = best_c > 0 ? best_d : min(max(0, -m), n);
-}
-
-// ---- both strands (mprime_anchor.h: ORIENTATION) -------------------------------------------------------------------------------------
-// the complement of an upper-cased letter: A<>T, C<>G, R<>Y, K<>M, B<>V, D<>H, U->A; S, W, N and every other byte as they are
-__host__ __device__ inline uint8_t complement_letter(uint8_t ch) {
-    switch (ch) {
-        case 'A': return 'T'; case 'T': return 'A'; case 'U': return 'A'; case 'C': return 'G'; case 'G': return 'C';
-        case 'R': return 'Y'; case 'Y': return 'R'; case 'K': return 'M'; case 'M': return 'K';
-        case 'B': return 'V'; case 'V': return 'B'; case 'D': return 'H'; case 'H': return 'D';
-        default: return ch;
-    }
-}
-
-// One pass of the vote over the wave's histogram (cleared on entry, all lanes), kRev: over the words of rc(q), read from the forward
-// bytes — the word of rc(q) at i' = m - 12 - i is the window q[i .. i + 12) with its letters complemented and their order reversed, so
-// its bin is j - i' + m.  Returns the best (votes, diagonal) in every lane; votes 0: no vote.
+// One pass of the vote over the wave's histogram hist[0 .. (m + n) / 2] (cleared on entry, all lanes): bin b = d + m (1 .. m + n - 1) is
+// counter (b & 1) of word b >> 1.  kRev: over the words of rc(q), read from the forward bytes — the word of rc(q) at i' = m - 12 - i is the
+// window q[i .. i + 12) with its letters complemented and their order reversed, so its bin is j - i' + m.  Returns the best (votes,
+// diagonal) in every lane; votes 0: no vote.  A second pass over the same histogram needs a barrier first: lanes still read it here.
 template <bool kRev>
-__device__ inline void orient_pass(uint32_t *hist, const uint8_t *qb, int m, int n, const uint32_t *__restrict__ akmer,
-                                   const int32_t *__restrict__ table, int log2_slots, int lane, int *best_c_out, int *best_d_out) {
+__device__ inline void vote_pass(uint32_t *hist, const uint8_t *qb, int m, int n, const uint32_t *__restrict__ akmer,
+                                 const int32_t *__restrict__ table, int log2_slots, int lane, int *best_c_out, int *best_d_out) {
     const int words = (m + n) / 2 + 1;
     for (int x = lane; x < words; x += 64) hist[x] = 0;
     __syncthreads();
     const uint32_t mask = (1u << log2_slots) - 1;
     for (int i = lane; i + kWord <= m && n >= kWord; i += 64) {
-        uint32_t kmer = 0;
-        bool ok = true;
-        for (int x = 0; x < kWord; x++) {
-            const int cd = kRev ? base_code(complement_letter(upper_letter(qb[i + kWord - 1 - x]))) : base_code(qb[i + x]);
-            ok = ok && cd < 4;
-            kmer = (kmer << 2) | (uint32_t)(cd & 3);
-        }
-        if (!ok) continue;
+        const uint32_t kmer = kRev ? seed_word_rc_letters(qb + i) : seed_word_letters(qb + i);
+        if (kmer == kEmpty) continue;
         const int iq = kRev ? m - kWord - i : i;
         uint32_t slot = word_hash(kmer, log2_slots);
         for (int32_t j; (j = table[slot]) >= 0; slot = (slot + 1) & mask)
@@ -128,11 +62,22 @@ __device__ inline void orient_pass(uint32_t *hist, const uint8_t *qb, int m, int
         const int oc = __shfl_xor(best_c, sh), od = __shfl_xor(best_d, sh);
         if (oc > 0 && (best_c == 0 || vote_better(oc, od, best_c, best_d))) { best_c = oc; best_d = od; }
     }
-    __syncthreads();                           // (every lane has read the histogram before the next pass clears it)
     *best_c_out = best_c;
     *best_d_out = best_d;
 }
 
+__global__ __launch_bounds__(64) void anchor_vote_kernel(const uint8_t *__restrict__ bytes, const int64_t *__restrict__ off, int n,
+                                                          const uint32_t *__restrict__ akmer, const int32_t *__restrict__ table, int log2_slots,
+                                                          int32_t *__restrict__ d0_out) {
+    extern __shared__ uint32_t hist[];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int m = (int)(off[q + 1] - off[q]);
+    int best_c, best_d;
+    vote_pass<false>(hist, bytes + off[q], m, n, akmer, table, log2_slots, lane, &best_c, &best_d);
+    if (lane == 0) d0_out[q] = best_c > 0 ? best_d : min(max(0, -m), n);
+}
+
+// ---- both strands (mprime_anchor.h: ORIENTATION) -------------------------------------------------------------------------------------
 // anchor_vote_kernel for both strands: one wavefront per query, the same histogram (up to (m + n) / 2 + 1 words) for the forward pass
 // and then for the pass over rc(q).  The query is turned iff rc(q)'s best diagonal has strictly more votes; then the wave rewrites the
 // query's bytes IN PLACE as rc(q) — lane x swaps the pair (x, m - 1 - x) through upper_letter and complement_letter, pairs are disjoint,
@@ -147,8 +92,9 @@ __global__ __launch_bounds__(64) void anchor_orient_kernel(uint8_t *__restrict__
     uint8_t *qb = bytes + off[q];
     const int m = (int)(off[q + 1] - off[q]);
     int cf, df, cr, dr;
-    orient_pass<false>(hist, qb, m, n, akmer, table, log2_slots, lane, &cf, &df);
-    orient_pass<true>(hist, qb, m, n, akmer, table, log2_slots, lane, &cr, &dr);
+    vote_pass<false>(hist, qb, m, n, akmer, table, log2_slots, lane, &cf, &df);
+    __syncthreads();                           // (every lane has read the histogram before the next pass clears it)
+    vote_pass<true>(hist, qb, m, n, akmer, table, log2_slots, lane, &cr, &dr);
     const bool turn = cr > cf;                 // (uniform over the wave: both reductions leave every lane with the same pair)
     if (turn) {
         for (int x = lane; x < m / 2; x += 64) {
@@ -171,9 +117,44 @@ __global__ __launch_bounds__(256) void anchor_mark_kernel(int32_t *__restrict__ 
     if (q < nq && flag[q]) meta[(size_t)q * MP_ANCHOR_META + 7] |= MP_ANCHOR_REVERSED;
 }
 
-// ---- the banded Gotoh sweep ----------------------------------------------------------------------------------------------------------
+// ---- the banded Gotoh sweep, traced ---------------------------------------------------------------------------------------------------
 // Traceback bits of cell (i, t), i = 1 .. m, t = diagonal index inside the band: nibble (i - 1) & 7 of word tb[tb_off[q] + ((i - 1) >> 3) *
 // 64 R + t]; bits 0-1: H came from 0 the diagonal, 1 E, 2 F (3: the cell lies outside the matrix); bit 2: E opened here; bit 3: F opened here.
+// band_sweep's payload: cell() and outside() form the cell's nibble, add() puts it into acc[r], which collects the nibbles of diagonal
+// slot r, eight rows (or the last rows up to m) to a stored word.  Where add() is called is a matter of speed alone (profiles/
+// bandsweep.txt): with R >= 4 from joined(), one store site per slot after the two paths have met — half the store sites and a fifth
+// fewer branches in the long unrolled step; with R <= 2 behind each of the two calls, where the short step runs 1 .. 3 % faster so.
+template <int R>
+struct TracePayload {
+    static constexpr bool kAddWhereJoined = R >= 4;
+    uint32_t *tbq;                             // the query's words
+    int m;
+    uint32_t acc[R];
+    uint32_t bits;                             // the nibble of the cell between its call and joined()
+    __device__ __forceinline__ void start(int r, bool) { acc[r] = 0; }
+    __device__ __forceinline__ void exchange() {}
+    __device__ __forceinline__ void add(int r, int t, int i) {
+        const int k = i - 1;
+        acc[r] |= bits << (4 * (k & 7));
+        if ((k & 7) == 7 || i == m) {
+            tbq[(size_t)(k >> 3) * (64 * R) + t] = acc[r];
+            acc[r] = 0;
+        }
+    }
+    __device__ __forceinline__ void outside(int r, int t, int i) {
+        bits = 3u;
+        if (!kAddWhereJoined) add(r, t, i);
+    }
+    __device__ __forceinline__ void cell(int r, int t, int i, int, bool, int h_source, bool e_opened, bool f_opened, bool) {
+        bits = (uint32_t)h_source | (e_opened ? 4u : 0u) | (f_opened ? 8u : 0u);
+        if (!kAddWhereJoined) add(r, t, i);
+    }
+    __device__ __forceinline__ void joined(int r, int t, int i) {
+        if (kAddWhereJoined) add(r, t, i);
+    }
+    __device__ __forceinline__ void finish(int, int) {}
+};
+
 // kList (star.hip's band escalation): work item x is record list[x] — d0v and end_out are indexed by the record, tb_off by the item, and the
 // item's words start at tb + tb_off[x] - tb_base (a chunk of a longer list).  Without it the item is the record and both are unused.
 template <int R, bool kList>
@@ -197,71 +178,11 @@ __global__ __launch_bounds__(256) void anchor_dp_kernel(const uint8_t *__restric
     }
     __syncthreads();                           // (the only barrier: what follows is per wave)
     if (item >= nq) return;
-    const int B = 2 * W + 1, dlo = d0v[q] - W, Bpad = 64 * R;
-    uint32_t *tbq = tb + (kList ? tb_off[item] - tb_base : tb_off[item]);
-    int H[R], E[R], F[R];
-    uint32_t acc[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int t = lane * R + r, d = dlo + t;
-        H[r] = (t < B && d >= 0 && d <= n) ? 0 : kNeg;          // the row-0 cell of the diagonal
-        E[r] = F[r] = kNeg;
-        acc[r] = 0;
-    }
-    const int s_end = 2 * m + dlo + B - 1;
-    for (int s = 2 + dlo; s <= s_end; s++) {
-        // the neighbouring lanes' edge diagonals as of step s - 1
-        int hl_edge = __shfl_up(H[R - 1], 1), el_edge = __shfl_up(E[R - 1], 1);
-        int hu_edge = __shfl_down(H[0], 1), fu_edge = __shfl_down(F[0], 1);
-        if (lane == 0) hl_edge = el_edge = kNeg;
-        if (lane == 63) hu_edge = fu_edge = kNeg;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int t = lane * R + r, d = dlo + t, two_i = s - d;
-            if ((two_i & 1) || two_i < 2 || two_i > 2 * m || t >= B) continue;       // (the cells of one step have one parity: H[r +- 1] are of step s - 1)
-            const int i = two_i >> 1, j = i + d;
-            int h = kNeg, e = kNeg, f = kNeg;
-            uint32_t bits = 3;
-            if (j >= 0 && j <= n) {
-                const int hl = r > 0 ? H[r > 0 ? r - 1 : 0] : hl_edge, el = r > 0 ? E[r > 0 ? r - 1 : 0] : el_edge;
-                const int hu = r < R - 1 ? H[r < R - 1 ? r + 1 : 0] : hu_edge, fu = r < R - 1 ? F[r < R - 1 ? r + 1 : 0] : fu_edge;
-                const int eo = hl - open_ext, ee = el - ext, fo = hu - open_ext, fe = fu - ext;
-                e = max(eo, ee);
-                f = max(fo, fe);
-                int dg = kNeg;
-                if (j >= 1) {
-                    const int qcd = qc[i - 1], acd = lds[j - 1];
-                    dg = H[r] + ((qcd < 4 && acd < 4) ? (qcd == acd ? match : -mismatch) : 0);
-                }
-                h = max(dg, max(e, f));
-                bits = (dg >= e && dg >= f) ? 0u : (e >= f ? 1u : 2u);
-                bits |= (eo >= ee ? 4u : 0u) | (fo >= fe ? 8u : 0u);
-                h = max(h, kNeg); e = max(e, kNeg); f = max(f, kNeg);
-            }
-            H[r] = h; E[r] = e; F[r] = f;
-            const int k = i - 1;
-            acc[r] |= bits << (4 * (k & 7));
-            if ((k & 7) == 7 || i == m) {
-                tbq[(size_t)(k >> 3) * Bpad + t] = acc[r];
-                acc[r] = 0;
-            }
-        }
-    }
-    // the end cell: the largest H(m, j) of the band, the smallest j (= the smallest t) among equals
-    int best = kNeg, best_t = 0x7fffffff;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int t = lane * R + r;
-        if (t < B && H[r] > best) { best = H[r]; best_t = t; }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const int ob = __shfl_xor(best, sh), ot = __shfl_xor(best_t, sh);
-        if (ob > best || (ob == best && ot < best_t)) { best = ob; best_t = ot; }
-    }
+    TracePayload<R> pay{tb + (kList ? tb_off[item] - tb_base : tb_off[item]), m};
+    const BandEnd end = band_sweep<R>(qc, lds, m, n, d0v[q] - W, W, match, mismatch, open_ext, ext, pay);
     if (lane == 0) {
-        const bool none = best < kNoPath;
-        end_out[2 * q] = none ? MP_ANCHOR_NO_SCORE : best;
-        end_out[2 * q + 1] = none ? -1 : best_t;
+        end_out[2 * q] = end.score;
+        end_out[2 * q + 1] = end.t;
     }
 }
 
@@ -350,9 +271,6 @@ __global__ __launch_bounds__(64) void anchor_trace_kernel(const uint8_t *__restr
     mt[6] = j_last >= 0 ? col[j_last] : -1;
     mt[7] = status; mt[8] = j_first; mt[9] = j_last;
 }
-
-// diagonals per lane of the sweep for a band of half width W: 2W + 1 <= 64 R
-inline int anchor_lane_diagonals(int W) { const int B = 2 * W + 1; return B <= 64 ? 1 : B <= 128 ? 2 : B <= 256 ? 4 : 8; }
 
 }  // namespace
 

@@ -1,6 +1,6 @@
 // cluster.hip — clustering by identity (include/mprime_cluster.h): greedy incremental clustering in rounds over blocks of candidate
 // representatives.  Kernels:
-//   cluster_index_kernel  one lane per base of the block's members: the 12-mer that starts there goes into one open-addressing table
+//   cluster_index_kernel  one lane per base of the block's members: the 12-mer that starts there (seedword.hpp) goes into one open-addressing table
 //                         of block positions (atomicCAS on the slot; every occurrence is kept, so a lookup walks to the first empty
 //                         slot and the order of insertion cannot show)
 //   cluster_count_kernel  one wavefront per query: the number of (query position, block position) word matches with members it may
@@ -11,12 +11,13 @@
 //                         members reaching min_votes are written to the candidate list behind ONE reservation per wave on the
 //                         list's cursor (no per-entry atomics on shared state: DESIGN 9.-2).  The list's order is arbitrary; the host
 //                         takes minima over it
-//   cluster_dp_kernel     one wavefront per candidate pair, the anti-diagonal sweep of anchor_dp_kernel (R = 1, 2, 4, 8 diagonals per
-//                         lane) without a traceback buffer: H, E and F each carry the n_match (and the "touched the band's edge"
-//                         flag) of the predecessor the traceback would choose, so the end cell holds the traced path's numbers.
-//                         Both sequences sit in the wave's LDS slice; the workgroup is 1 .. 4 waves by the pair's lengths
+//   cluster_dp_kernel     one wavefront per candidate pair: band_sweep (bandsweep.hpp: the recurrence, its comparison order and the end
+//                         cell, R = 1, 2, 4, 8 diagonals per lane) with the CARRIED-COUNT payload instead of a traceback buffer: H, E
+//                         and F each carry the n_match (and the "touched the band's edge" flag) of the predecessor the traceback
+//                         would choose, so the end cell holds the traced path's numbers.  Both sequences sit in the wave's LDS
+//                         slice; the workgroup is 1 .. 4 waves by the pair's lengths
 // The greedy driver, the batching and mp_cluster_pairs are host code below.
-#include "common.hpp"
+#include "bandsweep.hpp"
 #include "seedword.hpp"
 #include "../../include/mprime_cluster.h"
 
@@ -24,25 +25,9 @@ namespace mp {
 
 namespace {
 
-constexpr int kNeg = -(1 << 30);               // as in anchor.hip: "no such cell"
-constexpr int kNoPath = -(3 << 28);
-constexpr int kWord = MP_ANCHOR_WORD;
 constexpr int kTouch = 1 << 16;                // above every n_match (<= 32767) in a carried count
 constexpr int kLdsSlots = 4096;                // vote table slots a wave keeps in LDS (keys + values: 32 KiB)
 constexpr int kRankTop = 131071;               // 17 bits: rank of a diagonal = 2 |d| + (d > 0), smaller is better
-
-// the 2-bit word starting at code[i] (12 letters), kEmpty when one of them is not A/C/G/T
-__device__ inline uint32_t word_at(const uint8_t *__restrict__ code, int i) {
-    uint32_t w = 0;
-    bool ok = true;
-#pragma unroll
-    for (int x = 0; x < kWord; x++) {
-        const uint32_t cd = code[i + x];
-        ok = ok && cd < 4;
-        w = (w << 2) | (cd & 3u);
-    }
-    return ok ? w : kEmpty;
-}
 
 __global__ __launch_bounds__(256) void cluster_code_kernel(const uint8_t *__restrict__ bytes, size_t total, uint8_t *__restrict__ code) {
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -77,7 +62,7 @@ __global__ __launch_bounds__(256) void cluster_index_kernel(const uint8_t *__res
     const int j = p - mpos[lo];
     const int64_t base = off[mem_seq[lo]];
     const int n = (int)(off[mem_seq[lo] + 1] - base);
-    const uint32_t w = j + kWord <= n ? word_at(code + base, j) : kEmpty;
+    const uint32_t w = j + kWord <= n ? seed_word_codes(code + base + j) : kEmpty;
     bkmer[p] = w;
     bmem[p] = (uint16_t)lo;
     if (w == kEmpty) return;
@@ -100,7 +85,7 @@ __global__ __launch_bounds__(256) void cluster_count_kernel(const uint8_t *__res
     const uint32_t mask = (1u << log2_slots) - 1;
     long long cnt = 0;
     for (int i = lane; i + kWord <= m; i += 64) {
-        const uint32_t w = word_at(qc, i);
+        const uint32_t w = seed_word_codes(qc + i);
         if (w == kEmpty) continue;
         uint32_t slot = word_hash(w, log2_slots);
         for (int32_t p; (p = table[slot]) >= 0; slot = (slot + 1) & mask) cnt += bkmer[p] == w && (int)bmem[p] < lim;
@@ -151,7 +136,7 @@ __global__ __launch_bounds__(64) void cluster_vote_kernel(const uint8_t *__restr
     const uint8_t *qc = code + base;
     const uint32_t mask = (1u << log2_slots) - 1;
     for (int i = lane; i + kWord <= m; i += 64) {
-        const uint32_t w = word_at(qc, i);
+        const uint32_t w = seed_word_codes(qc + i);
         if (w == kEmpty) continue;
         uint32_t slot = word_hash(w, log2_slots);
         for (int32_t p; (p = table[slot]) >= 0; slot = (slot + 1) & mask) {
@@ -211,9 +196,46 @@ __global__ __launch_bounds__(64) void cluster_vote_kernel(const uint8_t *__restr
 }
 
 // ---- the banded Gotoh sweep with carried counts ------------------------------------------------------------------------------------------
-// pairs: {query sequence, anchor sequence, d0, -}; out: {score, n_match, status, -}.  The recurrence, the order of its comparisons and
-// the end cell are anchor_dp_kernel's; where that kernel stores a predecessor bit, this one copies the predecessor's count.  A count
-// also carries kTouch once a cell of its path lies on the band's first or last diagonal.
+// band_sweep's payload: H, E and F of every diagonal slot carry the n_match of the path that leads there — the predecessor's count
+// by the flags the sweep hands over, one more on a diagonal move that pairs two equal letters.  A count also carries kTouch once a cell
+// of its path lies on the band's first or last diagonal.  The end cell's count is the traced path's.
+template <int R>
+struct CountPayload {
+    int HM[R], EM[R], FM[R];
+    int hml_edge, eml_edge, hmu_edge, fmu_edge;        // the neighbouring lanes' edge slots as of the step before
+    int carried = 0;                                   // the end cell's count
+    __device__ __forceinline__ void start(int r, bool on_edge) {
+        HM[r] = on_edge ? kTouch : 0;
+        EM[r] = FM[r] = 0;
+    }
+    __device__ __forceinline__ void exchange() {
+        hml_edge = __shfl_up(HM[R - 1], 1); eml_edge = __shfl_up(EM[R - 1], 1);
+        hmu_edge = __shfl_down(HM[0], 1); fmu_edge = __shfl_down(FM[0], 1);
+    }
+    // An outside cell keeps whatever its slot carries (as lane 0's left and lane 63's upper edge do, which nobody sets).  That rests on
+    // bandsweep.hpp's kNeg < kNoPath and on mprime_anchor.h's limits, (m + n) * MP_ANCHOR_MAX_PARAM < 2^28: an outside cell scores kNeg,
+    // everything fed by it alone stays below kNoPath, every score fed by row 0 lies above kNoPath, and a predecessor is chosen by the
+    // larger score — so a count that passed through an outside cell is never the one of a reported end cell (none: n_match 0, status 3).
+    __device__ __forceinline__ void outside(int, int, int) {}
+    __device__ __forceinline__ void cell(int r, int, int, int j, bool on_edge, int h_source, bool e_opened, bool f_opened, bool is_match) {
+        const int edge = on_edge ? kTouch : 0;
+        const int hml = r > 0 ? HM[r > 0 ? r - 1 : 0] : hml_edge, eml = r > 0 ? EM[r > 0 ? r - 1 : 0] : eml_edge;
+        const int hmu = r < R - 1 ? HM[r < R - 1 ? r + 1 : 0] : hmu_edge, fmu = r < R - 1 ? FM[r < R - 1 ? r + 1 : 0] : fmu_edge;
+        const int em = (e_opened ? hml : eml) | edge, fm = (f_opened ? hmu : fmu) | edge;
+        const int dgm = j >= 1 ? (HM[r] + (is_match ? 1 : 0)) | edge : 0;
+        HM[r] = h_source == kFromDiag ? dgm : (h_source == kFromE ? em : fm);
+        EM[r] = em; FM[r] = fm;
+    }
+    __device__ __forceinline__ void joined(int, int, int) {}
+    __device__ __forceinline__ void finish(int lane, int r) {
+        int mine = 0;
+#pragma unroll
+        for (int x = 0; x < R; x++) if (x == r) mine = HM[x];
+        carried = __shfl(mine, lane);
+    }
+};
+
+// pairs: {query sequence, anchor sequence, d0, -}; out: {score, n_match, status, -}
 template <int R>
 __global__ __launch_bounds__(256) void cluster_dp_kernel(const uint8_t *__restrict__ code, const int64_t *__restrict__ off,
                                                           const int4 *__restrict__ pairs, int np, int W, int match, int mismatch, int open_ext, int ext,
@@ -235,70 +257,14 @@ __global__ __launch_bounds__(256) void cluster_dp_kernel(const uint8_t *__restri
     }
     __syncthreads();                           // (the only barrier: what follows is per wave)
     if (p >= np) return;
-    const int B = 2 * W + 1, dlo = d0 - W;
-    int H[R], E[R], F[R], HM[R], EM[R], FM[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int t = lane * R + r, d = dlo + t;
-        H[r] = (t < B && d >= 0 && d <= n) ? 0 : kNeg;          // the row-0 cell of the diagonal
-        E[r] = F[r] = kNeg;
-        HM[r] = (t == 0 || t == B - 1) ? kTouch : 0;
-        EM[r] = FM[r] = 0;
-    }
-    const int s_end = 2 * m + dlo + B - 1;
-    for (int s = 2 + dlo; s <= s_end; s++) {
-        int hl_edge = __shfl_up(H[R - 1], 1), el_edge = __shfl_up(E[R - 1], 1), hml_edge = __shfl_up(HM[R - 1], 1), eml_edge = __shfl_up(EM[R - 1], 1);
-        int hu_edge = __shfl_down(H[0], 1), fu_edge = __shfl_down(F[0], 1), hmu_edge = __shfl_down(HM[0], 1), fmu_edge = __shfl_down(FM[0], 1);
-        if (lane == 0) hl_edge = el_edge = kNeg;
-        if (lane == 63) hu_edge = fu_edge = kNeg;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int t = lane * R + r, d = dlo + t, two_i = s - d;
-            if ((two_i & 1) || two_i < 2 || two_i > 2 * m || t >= B) continue;
-            const int i = two_i >> 1, j = i + d;
-            int h = kNeg, e = kNeg, f = kNeg, hm = 0, em = 0, fm = 0;
-            if (j >= 0 && j <= n) {
-                const int edge = (t == 0 || t == B - 1) ? kTouch : 0;
-                const int hl = r > 0 ? H[r > 0 ? r - 1 : 0] : hl_edge, el = r > 0 ? E[r > 0 ? r - 1 : 0] : el_edge;
-                const int hml = r > 0 ? HM[r > 0 ? r - 1 : 0] : hml_edge, eml = r > 0 ? EM[r > 0 ? r - 1 : 0] : eml_edge;
-                const int hu = r < R - 1 ? H[r < R - 1 ? r + 1 : 0] : hu_edge, fu = r < R - 1 ? F[r < R - 1 ? r + 1 : 0] : fu_edge;
-                const int hmu = r < R - 1 ? HM[r < R - 1 ? r + 1 : 0] : hmu_edge, fmu = r < R - 1 ? FM[r < R - 1 ? r + 1 : 0] : fmu_edge;
-                const int eo = hl - open_ext, ee = el - ext, fo = hu - open_ext, fe = fu - ext;
-                e = max(eo, ee);
-                em = (eo >= ee ? hml : eml) | edge;
-                f = max(fo, fe);
-                fm = (fo >= fe ? hmu : fmu) | edge;
-                int dg = kNeg, dgm = 0;
-                if (j >= 1) {
-                    const int qcd = qc[i - 1], acd = ac[j - 1];
-                    const bool both = qcd < 4 && acd < 4;
-                    dg = H[r] + (both ? (qcd == acd ? match : -mismatch) : 0);
-                    dgm = (HM[r] + (both && qcd == acd ? 1 : 0)) | edge;
-                }
-                h = max(dg, max(e, f));
-                hm = (dg >= e && dg >= f) ? dgm : (e >= f ? em : fm);
-                h = max(h, kNeg); e = max(e, kNeg); f = max(f, kNeg);
-            }
-            H[r] = h; E[r] = e; F[r] = f;
-            HM[r] = hm; EM[r] = em; FM[r] = fm;
-        }
-    }
-    int best = kNeg, best_t = 0x7fffffff, best_m = 0;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int t = lane * R + r;
-        if (t < B && H[r] > best) { best = H[r]; best_t = t; best_m = HM[r]; }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const int ob = __shfl_xor(best, sh), ot = __shfl_xor(best_t, sh), om = __shfl_xor(best_m, sh);
-        if (ob > best || (ob == best && ot < best_t)) { best = ob; best_t = ot; best_m = om; }
-    }
+    CountPayload<R> pay;
+    const BandEnd end = band_sweep<R>(qc, ac, m, n, d0 - W, W, match, mismatch, open_ext, ext, pay);
     if (lane == 0) {
-        const bool none = best < kNoPath;
-        const int n_match = none ? 0 : (best_m & (kTouch - 1));
-        int status = none ? 3 : ((best_m & kTouch) ? 2 : 0);
+        const bool none = end.t < 0;
+        const int n_match = none ? 0 : (pay.carried & (kTouch - 1));
+        int status = none ? 3 : ((pay.carried & kTouch) ? 2 : 0);
         if ((long long)n_match * 1000 < (long long)permille * m) status |= 1;
-        out[p] = make_int4(none ? MP_ANCHOR_NO_SCORE : best, n_match, status, 0);
+        out[p] = make_int4(end.score, n_match, status, 0);
     }
 }
 
@@ -505,7 +471,7 @@ struct Run {
     int align(const std::vector<PairIn> &pairs, std::vector<PairOut> *out) {
         out->assign(pairs.size(), PairOut{MP_ANCHOR_NO_SCORE, 0, 3, 0});
         if (pairs.empty()) return MP_OK;
-        const int W = par.band, B = 2 * W + 1, R = B <= 64 ? 1 : B <= 128 ? 2 : B <= 256 ? 4 : 8;
+        const int W = par.band, B = 2 * W + 1;
         auto stride_of = [&](const PairIn &p) { return (int)(((len(p.r) + 15) & ~15LL) + ((len(p.q) + 15) & ~15LL)); };
         // long pairs first: a launch takes pairs whose LDS slices differ by less than two, its workgroup as many waves as 32 KiB hold (1 .. 4)
         std::vector<uint32_t> order(pairs.size());
@@ -527,12 +493,11 @@ struct Run {
                 const size_t lds = (size_t)wpb * (size_t)stride;       // at most 64 KiB: one wave, two sequences of 32767 bases
                 const int np = (int)(b - a);
                 const dim3 grid((unsigned)((np + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
-#define MP_CLUSTER_DP(RR)                                                                                                                        \
-                hipLaunchKernelGGL((cluster_dp_kernel<RR>), grid, block, lds, c->stream, (const uint8_t *)c->cl_code, (const int64_t *)c->cl_off,   \
-                                   (const int4 *)(d_pairs + a), np, W, (int)par.match, (int)par.mismatch, (int)(par.gap_open + par.gap_extend),     \
-                                   (int)par.gap_extend, (int)par.identity_permille, stride, d_out + a)
-                if (R == 1) MP_CLUSTER_DP(1); else if (R == 2) MP_CLUSTER_DP(2); else if (R == 4) MP_CLUSTER_DP(4); else MP_CLUSTER_DP(8);
-#undef MP_CLUSTER_DP
+                for_lane_diagonals(W, [&](auto r) {
+                    hipLaunchKernelGGL((cluster_dp_kernel<decltype(r)::value>), grid, block, lds, c->stream, (const uint8_t *)c->cl_code,
+                                       (const int64_t *)c->cl_off, (const int4 *)(d_pairs + a), np, W, (int)par.match, (int)par.mismatch,
+                                       (int)(par.gap_open + par.gap_extend), (int)par.gap_extend, (int)par.identity_permille, stride, d_out + a);
+                });
                 if ((rc = dev(hipGetLastError(), "cluster_dp_kernel"))) return rc;
                 a = b;
             }

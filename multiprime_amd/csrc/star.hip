@@ -1,5 +1,6 @@
 // star.hip — the star alignment (include/mprime_star.h): one round aligns every resident record to an anchor with the vote, sweep and
-// traceback kernels of anchorcore.hpp and turns the N pairwise paths into one alignment that keeps every inserted base.  New here:
+// traceback kernels of anchorcore.hpp (the sweep's rule and the launch over its R forms: bandsweep.hpp) and turns the N pairwise paths into
+// one alignment that keeps every inserted base.  New here:
 //   path store            the traceback (kStore) notes per record and slot the inserted run's length and first query base: two
 //                         uint16 [N][S] planes, S = n + 1 rounded up to 8 so that a record's slots start on 16 bytes
 //   star_flag_kernel      band escalation: the records of a batch whose path touched the band (or found none) as an ascending list with
@@ -319,7 +320,7 @@ int mp_star_round(mp_ctx *c, const uint8_t *anchor, int32_t n, const mp_anchor_p
     const size_t tb_budget = std::max<size_t>(free_b / 4 / sizeof(uint32_t), (size_t)1 << 22);      // words
     long long cap_q = 1 << 20;
     if (const char *s = getenv("MP_STAR_BATCH")) { const long long v = atoll(s); if (v > 0) cap_q = std::min(v, cap_q); }
-    const int R0 = anchor_lane_diagonals(W0);
+    const int R0 = lane_diagonals(W0);
     std::vector<int32_t> bstart{0};
     size_t tb_cap = 0, max_q = 0;
     int max_m = 0;
@@ -376,17 +377,17 @@ int mp_star_round(mp_ctx *c, const uint8_t *anchor, int32_t n, const mp_anchor_p
     const int32_t *no_list = nullptr;
     // sweep + traceback of `items` work items at band W: the records q0 .. q0 + items (list == null) or list[0 .. items)
     auto align = [&](int W, int items, int q0, const int32_t *list, const int64_t *tboff, long long tb_base) {
-        const int R = anchor_lane_diagonals(W);
+        const int R = lane_diagonals(W);
         const dim3 grid((unsigned)((items + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
         const int64_t *offp = c->st_off + q0;
         const int32_t *d0p = c->st_d0 + q0;
         int32_t *endp = c->st_end + 2 * (size_t)q0;
-#define MP_STAR_DP(RR, LL)                                                                                                                        \
-        hipLaunchKernelGGL((anchor_dp_kernel<RR, LL>), grid, block, dp_lds, c->stream, (const uint8_t *)c->st_bytes, offp, items, d0p,                \
-                           (const uint8_t *)c->an_code, n, W, (int)p->match, (int)p->mismatch, oe, ext, mstride, d_tb, tboff, endp, list, tb_base)
-        if (list) { if (R == 1) MP_STAR_DP(1, true); else if (R == 2) MP_STAR_DP(2, true); else if (R == 4) MP_STAR_DP(4, true); else MP_STAR_DP(8, true); }
-        else { if (R == 1) MP_STAR_DP(1, false); else if (R == 2) MP_STAR_DP(2, false); else if (R == 4) MP_STAR_DP(4, false); else MP_STAR_DP(8, false); }
-#undef MP_STAR_DP
+        auto sweep = [&](auto r, auto listed) {
+            hipLaunchKernelGGL((anchor_dp_kernel<decltype(r)::value, decltype(listed)::value>), grid, block, dp_lds, c->stream, (const uint8_t *)c->st_bytes,
+                               offp, items, d0p, (const uint8_t *)c->an_code, n, W, (int)p->match, (int)p->mismatch, oe, ext, mstride, d_tb, tboff, endp,
+                               list, tb_base);
+        };
+        for_lane_diagonals(W, [&](auto r) { if (list) sweep(r, std::true_type{}); else sweep(r, std::false_type{}); });
         if (!launched() || !mark(1)) return false;
 #define MP_STAR_TRACE(LL)                                                                                                                         \
         hipLaunchKernelGGL((anchor_trace_kernel<LL, true>), dim3((unsigned)((items + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)c->st_bytes,  \
@@ -428,7 +429,7 @@ int mp_star_round(mp_ctx *c, const uint8_t *anchor, int32_t n, const mp_anchor_p
         // band escalation: the flagged records of this batch again at twice the band, until none is left or the band is the widest
         for (int W = W0; W < MP_ANCHOR_MAX_BAND;) {
             W = std::min(2 * W, MP_ANCHOR_MAX_BAND);
-            const int Bpad = 64 * anchor_lane_diagonals(W);
+            const int Bpad = 64 * lane_diagonals(W);
             hipLaunchKernelGGL(star_flag_kernel, dim3(1), dim3(kFlagThreads), 0, c->stream, (const int32_t *)c->st_meta, (const int64_t *)c->st_off, (int)q0,
                                (int)nb, Bpad, W, d_list, d_tboff, c->st_wfin, d_flag);
             if (!launched() || !mark(2)) return dev_fail();

@@ -1,6 +1,7 @@
 """Clustering by identity on the device (csrc/cluster.hip behind mp_cluster_load / mp_cluster_pairs / mp_cluster_greedy) against the
 yardstick of tests/cluster_ref.py on the cases of tests/cluster_cases.py: the pair records over all ordered pairs and every band form,
-the carried-count kernel against the traced one of anchored alignment, the LDS sizing at the length limit, the greedy result for every
+the carried-count kernel against the traced one of anchored alignment, the bands on either side of every change of the sweep's lane
+form, the LDS sizing at the length limit, the greedy result for every
 block size and pair batch, and the script end to end."""
 import os
 import subprocess
@@ -9,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import anchor_ref
 import cluster_cases as cases
 import cluster_ref as ref
 from conftest import REPO
@@ -17,6 +19,12 @@ from multiprime_amd.cluster import ClusterByIdentity
 
 FIELDS = ("votes", "d0", "score", "n_match", "status")
 BANDS = (0, 4, 32, 100, 255)
+# 2W + 1 = 63, 127 | 129, 255 | 257 diagonals: the widest band of a lane form (1, 2, 4 diagonals per lane) and the narrowest of the next
+EDGE_BANDS = (31, 63, 64, 127, 128)
+# twelve records of pair_case() — 8 .. 13, 64, 126, 128 and 172 bases of four families — all ordered pairs aligned (min_votes = 0)
+EDGE_RECORDS = (1, 2, 3, 6, 13, 16, 18, 34, 39, 43, 47, 58)
+# what the yardstick alone finds among the 144 pairs per band: (paths that touch the band's edge, paths with an indel, status 0)
+EDGE_KINDS = {31: (2, 60, 14), 63: (3, 87, 18), 64: (7, 89, 17), 127: (1, 104, 19), 128: (1, 104, 19)}
 IDENTITIES = (800, 900, 1000)
 SCRIPT = os.path.join(REPO, "scripts", "cluster_by_identity.py")
 
@@ -36,6 +44,24 @@ def pair_truth():
     q, r = np.divmod(np.arange(len(seqs) ** 2), len(seqs))
     want = {W: [ref.pair(seqs[a], seqs[b], band=W, identity_permille=800) for a, b in zip(q, r)] for W in BANDS}
     return seqs, q.astype(np.int32), r.astype(np.int32), want
+
+
+@pytest.fixture(scope="module")
+def edge_truth():
+    """EDGE_RECORDS, all ordered pairs, the yardstick's record of every pair per EDGE_BANDS band, and per band how many of the
+    alignments hold an indel (ref.pair's records do not keep the gap counts: anchor_ref.align is asked again, as ref.pair asks it)."""
+    records = cases.pair_case()
+    seqs = [records[k][1] for k in EDGE_RECORDS]
+    q, r = np.divmod(np.arange(len(seqs) ** 2), len(seqs))
+    want, indels = {}, {}
+    for W in EDGE_BANDS:
+        want[W] = [ref.pair(seqs[a], seqs[b], band=W, identity_permille=800, min_votes=0) for a, b in zip(q, r)]
+        indels[W] = 0
+        for a, b, w in zip(q, r, want[W]):
+            al = anchor_ref.align(seqs[a].upper(), seqs[b].upper(), list(range(len(seqs[b]))), len(seqs[b]), band=W, min_identity_permille=800, d0=w["d0"])
+            assert (al["score"], al["n_match"], al["status"]) == (w["score"], w["n_match"], w["status"])
+            indels[W] += al["score"] != ref.NO_SCORE and al["n_ins"] + al["n_del"] > 0
+    return seqs, q.astype(np.int32), r.astype(np.int32), want, indels
 
 
 @pytest.fixture(scope="module")
@@ -95,6 +121,33 @@ def test_carried_counts_equal_the_traced_alignment(W, hip_lib, pair_truth):
     try:
         ctx.cluster_load(data, off)
         got = ctx.cluster_pairs(q, r, band=W, identity_permille=800, min_votes=0).reshape(n, n, 5)
+        for b in range(n):
+            ctx.anchor_set(seqs[b].upper().encode(), np.arange(len(seqs[b])), len(seqs[b]), band=W, min_identity_permille=800)
+            _, meta, _ = ctx.anchor_align(data, off)
+            for key, col in (("score", 0), ("d0", 1), ("n_match", 2), ("status", 7)):
+                assert got[:, b, FIELDS.index(key)].tolist() == meta[:, col].tolist(), (W, b, key)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W", EDGE_BANDS)
+def test_bands_at_the_changes_of_the_lane_form(W, hip_lib, edge_truth):
+    """The last band of one lane form and the first of the next: the carried counts against the yardstick and against the traced
+    alignment, on pairs of which the yardstick says that some touch the band's edge, some hold an indel and some are clean."""
+    seqs, q, r, want, indels = edge_truth
+    n = len(seqs)
+    touched = sum(bool(w["status"] & 2) and w["score"] != ref.NO_SCORE for w in want[W])
+    clean = sum(w["status"] == 0 for w in want[W])
+    assert (touched, indels[W], clean) == EDGE_KINDS[W] and min(EDGE_KINDS[W]) >= 1
+    data, off = pack(seqs)
+    ctx = hip_lib.context(0)
+    try:
+        ctx.cluster_load(data, off)
+        got = ctx.cluster_pairs(q, r, band=W, identity_permille=800, min_votes=0)
+        for x, (g, w) in enumerate(zip(got.tolist(), want[W])):
+            assert dict(zip(FIELDS, g)) == w, (W, int(q[x]), int(r[x]), g, w)
+        got = got.reshape(n, n, 5)
         for b in range(n):
             ctx.anchor_set(seqs[b].upper().encode(), np.arange(len(seqs[b])), len(seqs[b]), band=W, min_identity_permille=800)
             _, meta, _ = ctx.anchor_align(data, off)
