@@ -44,7 +44,28 @@
  * step that made the clusters (the record is named); s outside 16 .. 1024; report_ppm outside 0 .. 1000000; an index or a group
  * outside the resident set.
  *
- * Not attempted: reverse-complement words (the clusters come from a forward-strand clustering), several GPUs.
+ * Not attempted: several GPUs.
+ *
+ * THE RULE, BOTH STRANDS (mp_ani_sketch_strands; off unless asked for — the rule above stays the rule of mp_ani_sketch)
+ *
+ * Canonical value.  A word has its forward value f as above.  Its reverse-complement word (the word reversed, A <-> T, C <-> G) has
+ * the value r.  The canonical value is cv = min(f, r).  An occurrence of a word is AS READ iff f == cv; a palindromic word (f == r)
+ * is always as read.
+ *
+ * Hash.  fmix32(cv).  cv is still a 24-bit value, so distinct canonical values have distinct hashes and none is 0xFFFFFFFF.
+ *
+ * Canonical sketch at size s.  The s smallest distinct hashes of the record's canonical values, ascending; FULL and empty as above.
+ *
+ * Orientation bit of a sketch element.  0 if the record holds at least one as-read occurrence of that canonical word, otherwise 1.
+ * (The canonical sketch of the reverse complement of a record has the same hashes; every bit is flipped but those of palindromic
+ * words and of words the record holds in both orientations, which are 0 on both sides.)
+ *
+ * A pair (A, B).  c, w, u, jq and ani_ppm exactly as above, on the canonical sketches.  In addition
+ *     same     the number of shared elements <= c whose two orientation bits are equal
+ *     opp      w - same
+ *
+ * Two groups (P, R).  n_rep and sum_ppm as above.  SAME and OPP are the sums of same and opp over the REPORTED pairs only.  The
+ * strand of P against R is '-' iff OPP > SAME, otherwise '+' (a tie, 0 / 0 included, is '+').
  *
  * HOW IT RUNS (results do not depend on any of it)
  *
@@ -56,6 +77,13 @@
  * output.  Integers make the order of those additions irrelevant.  A launch stays below the runtime's limit of 2^32 work-items: more
  * work than that goes out as several launches that add into the same outputs (MP_ANI_MAX_GRID=<workgroups> lowers the cap, read per
  * call).
+ *
+ * mp_ani_sketch_strands: the same kernel in a second form.  A lane rolls the reverse-complement word beside the forward one (primed
+ * over the same 11 letters, valid with it) and hashes the smaller; sort and compaction are the forward form's, and the compacted
+ * sketch also stays in 4 KiB of LDS.  Then every lane walks its positions once more, looks the hash of each as-read occurrence up in
+ * that sketch and sets a bit in a 128-byte LDS array; the complement goes out.  The comparison kernels run on a canonical set as
+ * they are.  mp_ani_pairs_strand is one wave per pair on the pair layout (first sketch and its bit words in the wave's LDS slice,
+ * the second in registers); mp_ani_groups_strand runs the group kernel's work list once more over the few decided group pairs.
  */
 #ifndef MPRIME_ANI_H
 #define MPRIME_ANI_H
@@ -96,6 +124,27 @@ int mp_ani_table(int32_t *out);
 /* ms[2] = {sketching (the last mp_ani_sketch), comparison (summed over the mp_ani_pairs / mp_ani_groups calls since)}: device event
  * times; counts[2] = {sketches resident, sequence pairs compared since the last mp_ani_sketch}. */
 int mp_ani_stats(struct mp_ctx *ctx, double *ms, int64_t *counts);
+
+/* ---- both strands (THE RULE, BOTH STRANDS) ---- */
+#define MP_ANI_OR_WORDS(s) (((s) + 31) / 32)   /* uint32 per sketch of orientation bits */
+
+/* mp_ani_sketch with canonical sketches and their orientation bits; arguments, refusals and replacement of the resident set as there.
+ * mp_ani_sketches, mp_ani_pairs, mp_ani_groups and mp_ani_stats serve a canonical set as they serve a forward one. */
+int mp_ani_sketch_strands(struct mp_ctx *ctx, int32_t n, const uint8_t *bytes, const int64_t *off, int32_t s);
+
+/* The orientation bits of the resident canonical set: bits[n][MP_ANI_OR_WORDS(s)], bit i % 32 of word i / 32 is entry i of the
+ * sketch; bits past a sketch's size are zero. */
+int mp_ani_orientations(struct mp_ctx *ctx, uint32_t *bits);
+
+/* (same, opp) of n_pairs pairs of resident canonical sketches: out[n_pairs][2].  The unit of the strand rule. */
+int mp_ani_pairs_strand(struct mp_ctx *ctx, int64_t n_pairs, const int32_t *a_idx, const int32_t *b_idx, int32_t *out);
+
+/* Groups and group pairs as in mp_ani_groups: out[x] = {SAME, OPP} over the pairs reported at the floor report_ppm. */
+int mp_ani_groups_strand(struct mp_ctx *ctx, int32_t n_groups, const int32_t *group_off, int64_t n_gp, const int32_t *q_group,
+                         const int32_t *r_group, int32_t report_ppm, int64_t *out);
+
+/* mp_ani_orientations, mp_ani_pairs_strand and mp_ani_groups_strand return MP_ERR_ARG, with a message, when the resident set is a
+ * forward one (mp_ani_sketch); their other argument checks are those of mp_ani_pairs and mp_ani_groups. */
 
 #ifdef __cplusplus
 }

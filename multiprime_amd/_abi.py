@@ -173,6 +173,14 @@ ANI_SYMBOLS = [
     ("mp_ani_table", C.c_int, [_p]),
     ("mp_ani_stats", C.c_int, [_p, _p, _p]),
 ]
+# both strands of include/mprime_ani.h: canonical sketches with orientation bits and the (same, opp) vote; the checker is
+# tests/ani_strand_ref.py
+ANI_STRAND_SYMBOLS = [
+    ("mp_ani_sketch_strands", C.c_int, [_p, C.c_int32, _p, _p, C.c_int32]),
+    ("mp_ani_orientations", C.c_int, [_p, _p]),
+    ("mp_ani_pairs_strand", C.c_int, [_p, C.c_int64, _p, _p, _p]),
+    ("mp_ani_groups_strand", C.c_int, [_p, C.c_int32, _p, C.c_int64, _p, _p, C.c_int32, _p]),
+]
 ANI_MIN_SKETCH = 16                 # MP_ANI_MIN_SKETCH
 ANI_MAX_SKETCH = 1024               # MP_ANI_MAX_SKETCH
 ANI_TABLE = 1025                    # MP_ANI_TABLE
@@ -316,6 +324,9 @@ class Library:
         self.ani = all(hasattr(self.dll, name) for name, _, _ in ANI_SYMBOLS)
         if self.backend == "hip" and not self.ani:
             raise MprimeError(-2, f"{path} lacks the identity-merge entry points of include/mprime_ani.h: rebuild it")
+        self.ani_strands = all(hasattr(self.dll, name) for name, _, _ in ANI_STRAND_SYMBOLS)
+        if self.backend == "hip" and not self.ani_strands:
+            raise MprimeError(-2, f"{path} lacks the both-strand entry points of include/mprime_ani.h: rebuild it")
         self.dege = all(hasattr(self.dll, name) for name, _, _ in DEGE_SYMBOLS)
         if self.backend == "hip" and not self.dege:
             raise MprimeError(-2, f"{path} lacks the DegePrime entry points of include/mprime_dege.h: rebuild it")
@@ -326,7 +337,7 @@ class Library:
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
                                 (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else []) +
                                 (DEGE_SYMBOLS if self.dege else []) + (ONT_SYMBOLS if self.ont else []) +
-                                (STRAND_SYMBOLS if self.strands else [])):
+                                (STRAND_SYMBOLS if self.strands else []) + (ANI_STRAND_SYMBOLS if self.ani_strands else [])):
             fn = getattr(self.dll, name)
             fn.restype = res
             fn.argtypes = args
@@ -1062,12 +1073,18 @@ class Context:
         if not self.lib.ani:
             raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_ani.h (libmprime_hip.so does)")
 
-    def ani_sketch(self, data, off, s: int = ANI_MAX_SKETCH):
-        """Sketch the sequences data[off[i]:off[i+1]] at size s and keep the sketches resident (mp_ani_sketch)."""
+    def _need_ani_strands(self):
         self._need_ani()
+        if not self.lib.ani_strands:
+            raise MprimeError(-2, f"{self.lib.path} has no both-strand entry points of include/mprime_ani.h")
+
+    def ani_sketch(self, data, off, s: int = ANI_MAX_SKETCH, strands: bool = False):
+        """Sketch the sequences data[off[i]:off[i+1]] at size s and keep the sketches resident (mp_ani_sketch); strands: canonical
+        sketches with their orientation bits (mp_ani_sketch_strands)."""
+        self._need_ani_strands() if strands else self._need_ani()
         data = np.ascontiguousarray(data, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.int64)
-        rc = self.d.mp_ani_sketch(self.h, len(off) - 1, _ptr(data), _ptr(off), int(s))
+        rc = (self.d.mp_ani_sketch_strands if strands else self.d.mp_ani_sketch)(self.h, len(off) - 1, _ptr(data), _ptr(off), int(s))
         if rc != 0 and rc != -1:                # (MP_ERR_ARG: refused before anything was touched, the earlier set stays resident)
             self.ani_n = 0
         self._ck(rc)
@@ -1100,6 +1117,36 @@ class Context:
         out = np.zeros((max(len(q_group), 1), 2), np.int64)
         self._ck(self.d.mp_ani_groups(self.h, len(group_off) - 1, _ptr(group_off), len(q_group), _ptr(q_group), _ptr(r_group), int(report_ppm),
                                       _ptr(out)))
+        return out[: len(q_group)]
+
+    def ani_orientations(self) -> np.ndarray:
+        """uint32 [n][(s + 31) // 32]: the orientation bits of the resident canonical sketches, bit i % 32 of word i // 32 for entry i
+        (mp_ani_orientations)."""
+        self._need_ani_strands()
+        n, s = getattr(self, "ani_n", 0), getattr(self, "ani_s", 0)
+        bits = np.zeros((max(n, 1), max((s + 31) // 32, 1)), np.uint32)
+        self._ck(self.d.mp_ani_orientations(self.h, _ptr(bits)))
+        return bits[:n]
+
+    def ani_pairs_strand(self, a_idx, b_idx) -> np.ndarray:
+        """int32 [n_pairs][2] = same, opp of canonical sketch a_idx[p] against canonical sketch b_idx[p] (mp_ani_pairs_strand)."""
+        self._need_ani_strands()
+        a_idx = np.ascontiguousarray(a_idx, dtype=np.int32)
+        b_idx = np.ascontiguousarray(b_idx, dtype=np.int32)
+        out = np.zeros((max(len(a_idx), 1), 2), np.int32)
+        self._ck(self.d.mp_ani_pairs_strand(self.h, len(a_idx), _ptr(a_idx), _ptr(b_idx), _ptr(out)))
+        return out[: len(a_idx)]
+
+    def ani_groups_strand(self, group_off, q_group, r_group, report_ppm: int = 700000) -> np.ndarray:
+        """int64 [n_gp][2] = SAME, OPP of group q_group[x] against group r_group[x] over the pairs reported at the floor
+        (mp_ani_groups_strand); groups as in ani_groups."""
+        self._need_ani_strands()
+        group_off = np.ascontiguousarray(group_off, dtype=np.int32)
+        q_group = np.ascontiguousarray(q_group, dtype=np.int32)
+        r_group = np.ascontiguousarray(r_group, dtype=np.int32)
+        out = np.zeros((max(len(q_group), 1), 2), np.int64)
+        self._ck(self.d.mp_ani_groups_strand(self.h, len(group_off) - 1, _ptr(group_off), len(q_group), _ptr(q_group), _ptr(r_group),
+                                             int(report_ppm), _ptr(out)))
         return out[: len(q_group)]
 
     def ani_table(self) -> np.ndarray:

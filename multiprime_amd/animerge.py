@@ -12,6 +12,10 @@ while the .txt lists at most 500 of its records, so there every record counts.
 The decision mirrors the reference (merge_cluster_app / high_ANI_selection) with one documented difference: the reference compares
 fastANI's identity in PERCENT with `-a 0.8`, so any pair fastANI reports merges; here -a is a fraction compared with the mean as a
 fraction, and --report-floor (default 0.7) is what "reported" means.  With -a <= floor the decisions are the reference's.
+
+--both-strands compares canonical sketches (fastANI maps both strands: a rare cluster that is the reverse complement of a larger one's
+neighbour merges), votes the strand of every decided merge from the sketches' orientation bits and writes <out>.strand; --orient
+appends a cluster merged on the other strand reverse-complemented.  Off by default, and then nothing changes.
 """
 from __future__ import annotations
 
@@ -23,9 +27,32 @@ import time
 
 import numpy as np
 
+from . import iupac
 from ._abi import ANCHOR_MAX_LEN, ANI_MAX_SKETCH, ANI_MIN_SKETCH, ANI_PPM, Library
 
 _EXTS = (".fa", ".tfa", ".txt")
+# the complement of iupac.py, for bytes, lower case to lower case; any other byte stays
+_COMP = bytes.maketrans(*(("".join(chr(k) for k in iupac._COMP) + "".join(chr(k).lower() for k in iupac._COMP)).encode(),
+                          ("".join(chr(v) for v in iupac._COMP.values()) + "".join(chr(v).lower() for v in iupac._COMP.values())).encode()))
+
+
+def revcomp_fasta(src, dst):
+    """Append the FASTA file src to dst with every record reverse-complemented: a header line ('>') byte for byte, the record's
+    sequence lines joined (stripped of white space at their ends), reversed and complemented, on one line."""
+    with open(src, "rb") as fi, open(dst, "ab") as fo:
+        seq = None                              # the sequence lines of the record being read; None before the first line of one
+
+        def flush():
+            if seq is not None:
+                fo.write(b"".join(seq).translate(_COMP)[::-1] + b"\n")
+        for line in fi:
+            if line.startswith(b">"):
+                flush()
+                seq = None
+                fo.write(line if line.endswith(b"\n") else line + b"\n")
+            elif line.strip():
+                seq = (seq or []) + [line.strip()]
+        flush()
 
 
 def _read_tfa(path):
@@ -43,7 +70,7 @@ def _read_tfa(path):
 
 class merge_clstr(object):
     def __init__(self, inputfile="", output="", threshold=20, drop="T", ani=0.8, nproc=10, sketch_size=ANI_MAX_SKETCH, report_floor=0.7,
-                 device=0, library=None, clusters=None):
+                 device=0, library=None, clusters=None, both_strands=False, orient=False):
         """`clusters`: [(name, size)] instead of reading `inputfile` — with load_records(), the device pass and decide() for a caller
         that holds the records in memory (apply() still works on the files)."""
         self.cluster_file = inputfile
@@ -55,6 +82,10 @@ class merge_clstr(object):
         self.ani = float(ani)
         self.sketch_size, self.report_floor = int(sketch_size), float(report_floor)
         self.device, self.library = device, library
+        self.both_strands, self.orient = bool(both_strands), bool(orient)
+        if self.orient and (not self.both_strands or drop == "T"):
+            raise ValueError("orient needs both_strands and a merge (-d other than T)")
+        self.strands = None                     # {(ref id, sub id): ('+' | '-', SAME, OPP)} of the decided merges (both_strands)
         if not ANI_MIN_SKETCH <= self.sketch_size <= ANI_MAX_SKETCH:
             raise ValueError(f"sketch size {self.sketch_size}: {ANI_MIN_SKETCH}..{ANI_MAX_SKETCH}")
         if not 0 <= self.ani <= 1:
@@ -134,6 +165,9 @@ class merge_clstr(object):
         if self._off is None:
             raise RuntimeError("merge_clstr: load() first")
         numbers = {}
+        if self.both_strands:
+            self.strands = {}
+            self.stats.update(strand_ms=0.0, n_minus=0)
         todo = self.visiting()
         if not todo or len(self._off) < 2:
             return numbers
@@ -146,7 +180,10 @@ class merge_clstr(object):
         size = [n for _, n in self.cluster]
         ctx = lib.context(self.device)
         try:
-            ctx.ani_sketch(self._data, self._off, self.sketch_size)
+            if self.both_strands:
+                ctx.ani_sketch(self._data, self._off, self.sketch_size, strands=True)
+            else:
+                ctx.ani_sketch(self._data, self._off, self.sketch_size)
             for r0 in range(0, len(self.cluster), block):
                 if not todo:
                     break
@@ -164,9 +201,26 @@ class merge_clstr(object):
                 todo = [p for p in todo if p not in taken]
             ms, counts = ctx.ani_stats()
             self.stats.update(ms, **counts)
+            if self.both_strands:
+                self.vote(ctx, numbers)
         finally:
             ctx.close()
         return numbers
+
+    def vote(self, ctx, numbers):
+        """The strand of every merge decide() takes from `numbers`: one ani_groups_strand call over the decided (sub, ref) pairs on
+        the resident canonical set fills self.strands."""
+        kept = self.merge_dict
+        pos = {self.ident(x): x for x in range(len(self.cluster))}
+        pairs = [(ref, sub) for ref, subs in self.decide(numbers).items() for sub in subs]
+        self.merge_dict = kept
+        self.strands = {}
+        t0 = time.time()
+        if pairs:
+            got = ctx.ani_groups_strand(self._group_off, [pos[sub] for _, sub in pairs], [pos[ref] for ref, _ in pairs], self.report_ppm).tolist()
+            for key, (same, opp) in zip(pairs, got):
+                self.strands[key] = ("-" if opp > same else "+", same, opp)
+        self.stats.update(strand_ms=(time.time() - t0) * 1e3, n_minus=sum(v[0] == "-" for v in self.strands.values()))
 
     # -- the decision --------------------------------------------------------------------------------------------------------------------
     def decide(self, numbers):
@@ -192,6 +246,13 @@ class merge_clstr(object):
                 for m in subs:
                     f.write(k + "\t" + m + "\n")
 
+    def write_strands(self):
+        """<out>.strand, a line per line of history.txt in its order: ref id, sub id, + or -, SAME, OPP."""
+        with open(self.out + ".strand", "w") as f:
+            for k, subs in self.merge_dict.items():
+                for m in subs:
+                    f.write("%s\t%s\t%s\t%d\t%d\n" % ((k, m) + tuple(self.strands[(k, m)])))
+
     # -- the files -----------------------------------------------------------------------------------------------------------------------
     def apply(self):
         md = self.merge_dict
@@ -213,9 +274,15 @@ class merge_clstr(object):
             for sub in md[ref]:
                 cur = moved.get(sub, sub)
                 n += int(cur.rsplit("_", 1)[1])
+                # orient: a sub on the other strand arrives reverse-complemented as a whole — its file holds what it took itself in its
+                # own orientation, so a chain composes
+                turn = self.orient and self.strands[(ref, sub)][0] == "-"
                 for ext in _EXTS:
-                    with open(cur + ext, "rb") as fi, open(ref + ext, "ab") as fo:
-                        shutil.copyfileobj(fi, fo)
+                    if turn and ext != ".txt":
+                        revcomp_fasta(cur + ext, ref + ext)
+                    else:
+                        with open(cur + ext, "rb") as fi, open(ref + ext, "ab") as fo:
+                            shutil.copyfileobj(fi, fo)
                     os.remove(cur + ext)
             final = stem + "_" + str(n)
             for ext in _EXTS:
@@ -230,6 +297,8 @@ class merge_clstr(object):
         t2 = time.time()
         self.decide(numbers)
         self.write_history()
+        if self.both_strands:
+            self.write_strands()
         print("start merging...." if self.drop != "T" else "start dropping...")
         self.apply()
         self.stats.update(load_s=t1 - t0, compare_s=t2 - t1, apply_s=time.time() - t2, n_clusters=len(self.cluster),
@@ -248,8 +317,17 @@ def parse_args(argv=None):
     p.add_argument("-o", "--out", type=str, default="history.txt", metavar="<file>", help="output: ref id <tab> merged id per line. Default: history.txt")
     p.add_argument("--sketch-size", type=int, default=ANI_MAX_SKETCH, metavar="<int>", help=f"hashes per sketch, {ANI_MIN_SKETCH}..{ANI_MAX_SKETCH}. Default: {ANI_MAX_SKETCH}")
     p.add_argument("--report-floor", type=float, default=0.7, metavar="<float>", help="a sequence pair below this identity is not reported (as fastANI reports nothing below ~0.7-0.8). Default: 0.7")
+    p.add_argument("--both-strands", action="store_true",
+                   help="compare on both strands (canonical 12-mers): a rare cluster that is the reverse complement of a larger one's neighbour merges too; "
+                        "writes <out>.strand (ref id, sub id, + or -, SAME, OPP per line of the history)")
+    p.add_argument("--orient", action="store_true",
+                   help="with --both-strands and -d other than T: a cluster merged on the other strand is appended reverse-complemented, so the receiving .fa / .tfa keep one orientation")
     p.add_argument("--device", type=int, default=0, help="GPU ordinal (default 0)")
     args = p.parse_args(argv)
+    if args.orient and not args.both_strands:
+        p.error("--orient needs --both-strands")
+    if args.orient and args.drop == "T":
+        p.error("--orient needs a merge: -d other than T")
     if not ANI_MIN_SKETCH <= args.sketch_size <= ANI_MAX_SKETCH:
         p.error(f"--sketch-size must be in {ANI_MIN_SKETCH}..{ANI_MAX_SKETCH}")
     if not 0 <= args.ani <= 1:
@@ -265,7 +343,7 @@ def main(argv=None):
     e1 = time.time()
     args = parse_args(argv)                     # exit status 2 on bad flags
     app = merge_clstr(inputfile=args.input, output=args.out, threshold=args.threshold, drop=args.drop, ani=args.ani, nproc=args.nproc,
-                      sketch_size=args.sketch_size, report_floor=args.report_floor, device=args.device)
+                      sketch_size=args.sketch_size, report_floor=args.report_floor, device=args.device, both_strands=args.both_strands, orient=args.orient)
     app.run()                                   # SystemExit with a message (status 1) on a missing or empty .tfa or an over-long record
     e2 = time.time()
     print("INFO {} Total times: {}".format(time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(time.time())), round(float(e2 - e1), 2)))

@@ -309,6 +309,8 @@ struct mp_ctx {
     int32_t *ani_sizes = nullptr;            // [ani_n]
     uint32_t *ani_tab = nullptr;             // [MP_ANI_TABLE]
     int32_t ani_n = 0, ani_s = 0;
+    uint32_t *ani_or = nullptr;              // [ani_n][(ani_s + 31) / 32] orientation bits of a canonical set (mp_ani_sketch_strands), else null
+    bool ani_strands = false;                // the resident set is a canonical one
     double ani_ms[2] = {0, 0};
     int64_t ani_counts[2] = {0, 0};
     // star alignment (star.hip, include/mprime_star.h): the records of mp_star_load, the last round's path store, columns, rows and counts

@@ -208,6 +208,11 @@ ani)             # profiles/ani_merge.txt: the identity merge on 2000 synthetic 
   timeout -k 10 300 python -m pytest tests/test_ani_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
   timeout -k 10 600 python tools/ani_bench.py run 2>&1 | tee $O/ani_merge.txt &&
   timeout -k 10 300 python tools/ani_bench.py table 2>&1 | tee -a $O/ani_merge.txt ;;
+ani_strands)     # profiles/strands.txt, section 4: the set of `ani` with every second rare cluster turned, forward and with both strands: sketch ms of the two forms, compare ms, the strand pass, merges with and without the flag
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_ani_strand_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 600 python tools/ani_bench.py strands 2>&1 | tee $O/ani_strands.txt ;;
 dege)            # profiles/dege.txt: DegePrime on the recorded 150 x 320 slice and on a synthetic 10^5 x 1000 alignment: stage ms from mp_dege_stats, wall time; then the kernels' shares (kernel trace of the same program, a run of its own)
   # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
   set -o pipefail
