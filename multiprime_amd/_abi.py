@@ -215,6 +215,13 @@ ONT_SYMBOLS = [
     ("mp_ont_stats", C.c_int, [_p, _p, _p]),
 ]
 ONT_MAX_LEN = 64                    # MP_ONT_MAX_LEN
+# include/mprime_panel.h: the panel update (cross-set dimer search in csrc/dimer.hip, class joins in csrc/offtarget.hip) — exported by
+# libmprime_hip.so only; the checker of these calls is the plain restatement of the rule in tests/panel_ref.py
+PANEL_SYMBOLS = [
+    ("mp_dimer_cross", C.c_int, [_p, C.c_int32, _p, _p, C.c_int32, _p, _p, _p, C.c_double, C.c_int64, _p, C.POINTER(C.c_int64)]),
+    ("mp_amplicon_join_classes", C.c_int, [_p, C.c_int64, _p, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
+    ("mp_offtarget_classes", C.c_int, [_p, C.c_int32, _p, _p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
+]
 ONT_Q_ROWS, ONT_Q_COLS = 129, 65    # MP_ONT_Q_ROWS, MP_ONT_Q_COLS
 
 
@@ -333,7 +340,10 @@ class Library:
         self.ont = all(hasattr(self.dll, name) for name, _, _ in ONT_SYMBOLS)
         if self.backend == "hip" and not self.ont:
             raise MprimeError(-2, f"{path} lacks the read-assignment entry points of include/mprime_ont.h: rebuild it")
-        for name, res, args in ((OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
+        self.panel = all(hasattr(self.dll, name) for name, _, _ in PANEL_SYMBOLS)
+        if self.backend == "hip" and not self.panel:
+            raise MprimeError(-2, f"{path} lacks the panel-update entry points of include/mprime_panel.h: rebuild it")
+        for name, res, args in ((PANEL_SYMBOLS if self.panel else []) + (OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
                                 (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else []) +
                                 (DEGE_SYMBOLS if self.dege else []) + (ONT_SYMBOLS if self.ont else []) +
@@ -883,6 +893,77 @@ class Context:
         self._ck(self.d.mp_offtarget_stats(self.h, _ptr(ms), _ptr(counts)))
         return (dict(zip(("scan_ms", "reduce_ms", "join_ms", "call_ms"), ms.tolist())),
                 dict(zip(("hits", "forward_sites", "reverse_sites", "products", "forward_genes", "reverse_genes", "both_genes"), counts.tolist())))
+
+    # include/mprime_panel.h
+    def _need_panel(self):
+        if not self.lib.panel:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_panel.h (libmprime_hip.so does)")
+
+    def dimer_cross(self, codes, off, jobs, loss_hit, dg_params, dg_limit: float, cap: int = 1 << 16) -> np.ndarray:
+        """Hit records [n][6] = (job, y, end length, end expansion, y expansion, idx) of the jobs [m][3] = (x, y_lo, y_hi), sorted by
+        (job, y).  A result larger than `cap` is searched again with the exact size."""
+        self._need_panel()
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 3)
+        loss_hit = np.ascontiguousarray(loss_hit, dtype=np.uint8)
+        dg_params = np.ascontiguousarray(dg_params, dtype=np.float64)
+        while True:
+            hits = np.empty((max(cap, 1), 6), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_dimer_cross(self.h, len(off) - 1, _ptr(codes), _ptr(off), len(jobs), _ptr(jobs), _ptr(loss_hit),
+                                           _ptr(dg_params), dg_limit, cap, _ptr(hits), C.byref(n)))
+            if n.value <= cap:
+                h = hits[: n.value]
+                return h[np.lexsort((h[:, 1], h[:, 0]))] if len(h) else h
+            cap = int(n.value)
+
+    def dimer_cross_raw(self, codes, off, jobs, loss_hit, dg_params, dg_limit: float, cap: int):
+        """One mp_dimer_cross call as it is: (the first min(cap, n) records in arrival order, n)."""
+        self._need_panel()
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 3)
+        loss_hit = np.ascontiguousarray(loss_hit, dtype=np.uint8)
+        dg_params = np.ascontiguousarray(dg_params, dtype=np.float64)
+        hits = np.empty((max(cap, 1), 6), np.int32)
+        n = C.c_int64(0)
+        self._ck(self.d.mp_dimer_cross(self.h, len(off) - 1, _ptr(codes), _ptr(off), len(jobs), _ptr(jobs), _ptr(loss_hit),
+                                       _ptr(dg_params), dg_limit, cap, _ptr(hits) if cap else None, C.byref(n)))
+        return hits[: min(cap, n.value)], int(n.value)
+
+    def amplicon_join_classes(self, sites, size_lo: int, size_hi: int, cap: int = 1 << 20) -> np.ndarray:
+        """The three class joins alone: sites [n][5] = (class, strand, row, position, read), strictly ascending in (class, strand, row,
+        position); products [n][7] = (row, start, stop, forward read, reverse read, length, join class)."""
+        self._need_panel()
+        sites = np.ascontiguousarray(sites, dtype=np.int32).reshape(-1, 5)
+        while True:
+            out = np.empty((max(cap, 1), 7), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_amplicon_join_classes(self.h, len(sites), _ptr(sites), int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
+            if n.value <= cap:
+                return out[: n.value]
+            cap = int(n.value)
+
+    def offtarget_classes(self, pat_codes, pat_off, read_id, read_class, max_mismatch, term: int, size_lo: int, size_hi: int,
+                          cap: int = 1 << 20) -> np.ndarray:
+        """offtarget_resident with a class (0 core, 1 new) per read: products [n][7] of the three class joins.  A result larger than
+        `cap` is fetched again with the exact size: the library kept it, nothing is scanned twice."""
+        self._need_panel()
+        pat_codes = np.ascontiguousarray(pat_codes, dtype=np.uint8)
+        pat_off = np.ascontiguousarray(pat_off, dtype=np.int32)
+        n_pat = len(pat_off) - 1
+        read_id = np.ascontiguousarray(read_id, dtype=np.int32)
+        read_class = np.ascontiguousarray(read_class, dtype=np.int32)
+        mm = np.ascontiguousarray(np.broadcast_to(np.asarray(max_mismatch, np.int32), (n_pat,)), dtype=np.int32)
+        while True:
+            out = np.empty((max(cap, 1), 7), np.int32)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_offtarget_classes(self.h, n_pat, _ptr(pat_codes), _ptr(pat_off), _ptr(read_id), _ptr(read_class), _ptr(mm),
+                                                 int(term), int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
+            if n.value <= cap:
+                return out[: n.value]
+            cap = int(n.value)
 
     # include/mprime_anchor.h
     def _need_anchor(self):

@@ -285,6 +285,10 @@ struct mp_ctx {
     std::vector<uint8_t> ot_key;
     double ot_ms[4] = {0, 0, 0, 0};
     int64_t ot_counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    // the class joins of the panel update (include/mprime_panel.h): the products of the last mp_offtarget_classes, seven int32 each, kept
+    // on the host side of the context for a repeat of the call with a larger cap (otc_key: its arguments; free_seq drops them)
+    std::vector<int32_t> otc_out;
+    std::vector<uint8_t> otc_key;
     // anchored alignment (anchor.hip, include/mprime_anchor.h): the anchor of mp_anchor_set and the times / counts of the last mp_anchor_align
     uint8_t *an_code = nullptr;              // [an_n] 0..3 = A, C, G, T, 4 = anything else
     uint32_t *an_kmer = nullptr;             // [an_n] 2-bit code of the 12-mer starting at j, kEmpty where it does not exist

@@ -1,6 +1,7 @@
 // dimer.hip — part of libmprime_hip.so: hand-written HIP (gfx950 / MI355X, wave64) behind the C ABI of
 // include/mprime.h.  3'-end dimer scans (finDimer, get_Maxprimerset, get_multiPrime) and pair coverage from sequence bitsets.
 #include "common.hpp"
+#include "../../include/mprime_panel.h"
 
 using namespace mp;
 
@@ -374,8 +375,10 @@ __device__ inline int pair_filter(const PrimRec<LONG> &X, const PrimRec<LONG> &Y
 }
 
 // The reference's search (longest end first, expansions of the end, expansions of y; first passing combination) over the end
-// lengths the filter left, looking for RC(end) only at the candidate offsets.
-template <bool LONG>
+// lengths the filter left, looking for RC(end) only at the candidate offsets.  FLUSH: the deltaG test counts only where the end
+// reaches the partner's 3' end (d2 == 0: finDimer, get_Maxprimerset, get_multiPrime); without it the test holds at any d2
+// (Primer_set_update.py:276, mp_dimer_cross).
+template <bool LONG, bool FLUSH = true>
 __device__ inline bool pair_search(const PrimRec<LONG> &X, const PrimRec<LONG> &Y, PairEnds E, int max_m, typename PrimTraits<LONG>::plane_t cand,
                                    const uint8_t *__restrict__ loss_hit, const double *__restrict__ dg, double dg_limit, int32_t (&rec)[4]) {
     typedef typename PrimTraits<LONG>::plane_t plane_t;
@@ -402,7 +405,7 @@ __device__ inline bool pair_search(const PrimRec<LONG> &X, const PrimRec<LONG> &
                 const int gc = gc_count(e, mask);
                 const int d2 = ly - l - idx;
                 bool hit = loss_hit[((size_t)l * (MP_DIMER_MAX_LEN + 1) + gc) * 64 + d2] != 0;
-                if (!hit && d2 == 0) hit = dm_delta_g(e, l, dg) < dg_limit;
+                if (!hit && (!FLUSH || d2 == 0)) hit = dm_delta_g(e, l, dg) < dg_limit;
                 if (hit) { rec[0] = l; rec[1] = (int32_t)ei; rec[2] = (int32_t)pi; rec[3] = idx; return true; }
             }
         }
@@ -490,6 +493,78 @@ __global__ __launch_bounds__(kBlock) void dimer_pairs_kernel(const PrimRec<LONG>
     const int max_m = pair_filter<LONG>(X, Y, E.l_lo, cand);
     int32_t rec[4];
     flags[p] = max_m >= E.l_lo && pair_search<LONG>(X, Y, E, max_m, cand, loss_hit, dg, dg_limit, rec) ? 1 : 0;
+}
+
+// Rectangular search between two sets (Primer_set_update.py:258-294, include/mprime_panel.h): workgroup = one job {x, y_lo, y_hi}, threads
+// stride over the partners y_lo .. y_hi - 1.  The two stages are those of dimer_rows_kernel — bit-plane filter, LDS queue of the survivors
+// searched with full waves, hits batched in LDS with one device atomic per flush — and the search is pair_search without the d2 == 0
+// condition on the deltaG test.  A record is {job, y, end length, end expansion, y expansion, idx}.
+//
+// Sizes, for the worst case that EVERY partner passes the filter and hits (one record per (job, partner) at most):
+//   queue   a drain happens as soon as kBlock entries wait, so before a stride at most kBlock - 1 wait and at most kBlock arrive:
+//           fewer than kCrossQueue = 2 kBlock entries at any time;
+//   hits    a drain adds at most kCrossQueue - 1 records; the buffer is flushed whenever another such drain might not fit
+//           (held + kCrossQueue > kCrossHits), so before a drain held <= kCrossHits - kCrossQueue and after it held < kCrossHits.
+// LDS: 24 KB of records + 6.5 KB of queue (64-bit planes) per workgroup: five workgroups per CU; the wave count, not LDS, bounds occupancy.
+// The queue length that decides "drain or not" is read between TWO barriers: no wave can enqueue for the next stride while another still
+// reads it, so all waves take the same branch and meet the same barriers.
+constexpr int kCrossQueue = 2 * kBlock, kCrossHits = 2 * kCrossQueue;
+static_assert(kCrossHits >= 2 * kCrossQueue, "a drain must fit behind what a skipped flush left");
+template <bool LONG>
+__global__ __launch_bounds__(kBlock) void dimer_cross_kernel(const DimerArgs A, const PrimRec<LONG> *__restrict__ prim, const int32_t *__restrict__ jobs) {
+    typedef typename PrimTraits<LONG>::plane_t plane_t;
+    __shared__ int32_t s_rec[kCrossHits][6];
+    __shared__ int32_t s_qy[kCrossQueue];
+    __shared__ plane_t s_qc[kCrossQueue];
+    __shared__ uint8_t s_qm[kCrossQueue];
+    __shared__ int s_n, s_q;
+    __shared__ unsigned long long s_base;
+    const int job = blockIdx.x;
+    const int x = jobs[3 * job], y0 = jobs[3 * job + 1], y1 = jobs[3 * job + 2];
+    const PrimRec<LONG> X = prim[x];
+    const PairEnds E = end_lengths(X.len, 0);                       // min(t, len x), t = 18 .. 5 (PU:195-202)
+    if (threadIdx.x == 0) { s_n = 0; s_q = 0; }
+    __syncthreads();
+    for (int yb = y0; yb < y1; yb += kBlock) {
+        const int y = yb + threadIdx.x;
+        const bool last = yb + kBlock >= y1;
+        if (y < y1) {
+            plane_t cand;
+            const int max_m = pair_filter<LONG>(X, prim[y], E.l_lo, cand);
+            if (max_m >= E.l_lo) {
+                const int at = atomicAdd(&s_q, 1);
+                s_qy[at] = y; s_qc[at] = cand; s_qm[at] = (uint8_t)max_m;
+            }
+        }
+        __syncthreads();
+        const int queued = s_q;
+        __syncthreads();
+        if (queued < kBlock && !last) continue;
+        for (int i = threadIdx.x; i < queued; i += kBlock) {
+            const int yq = s_qy[i];
+            int32_t rec[4];
+            if (pair_search<LONG, false>(X, prim[yq], E, s_qm[i], s_qc[i], A.loss_hit, A.dg, A.dg_limit, rec)) {
+                const int at = atomicAdd(&s_n, 1);
+                int32_t *r = s_rec[at];
+                r[0] = job; r[1] = yq; r[2] = rec[0]; r[3] = rec[1]; r[4] = rec[2]; r[5] = rec[3];
+            }
+        }
+        __syncthreads();
+        const int held = s_n;
+        if (threadIdx.x == 0) s_q = 0;
+        if (held && (held + kCrossQueue > kCrossHits || last)) {
+            if (threadIdx.x == 0) s_base = atomicAdd(A.n_hits, (unsigned long long)held);
+            __syncthreads();
+            const unsigned long long base = s_base;
+            for (int i = threadIdx.x; i < held * 6; i += kBlock) {
+                const unsigned long long h = base + (unsigned long long)(i / 6);
+                if ((long long)h < A.cap) A.hits[6 * h + i % 6] = s_rec[i / 6][i % 6];
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) s_n = 0;
+        }
+        __syncthreads();
+    }
 }
 
 // popcount(A[i] | B[j]) per pair: one wave per pair, lanes stride over the set's words (get_multiPrime_V8.py:560-569)
@@ -991,6 +1066,56 @@ int mp_dimer_pairs(mp_ctx *c, int32_t n, const uint8_t *codes, const int32_t *of
     HIPCK(c, hipGetLastError());
     HIPCK(c, hipMemcpyAsync(flags, d_flags, (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    return MP_OK;
+}
+
+// include/mprime_panel.h
+int mp_dimer_cross(mp_ctx *c, int32_t n, const uint8_t *codes, const int32_t *off, int32_t n_jobs, const int32_t *jobs,
+                   const uint8_t *loss_hit, const double *dg, double dg_limit, int64_t cap, int32_t *hits, int64_t *n_hits) {
+    if (!c) return MP_ERR_ARG;
+    if (n < 0 || !codes || !off || n_jobs < 0 || (n_jobs && !jobs) || !loss_hit || !dg || !n_hits || cap < 0 || (cap && !hits))
+        return fail(c, MP_ERR_ARG, "mp_dimer_cross: bad arguments");
+    HIPCK(c, hipSetDevice(c->dev));
+    *n_hits = 0;
+    if (n == 0 || n_jobs == 0) return MP_OK;
+    int rc, longest = 0;
+    if ((rc = check_primers(c, n, codes, off, MP_DIMER_MAX_LEN, &longest))) return rc;
+    for (int32_t j = 0; j < n_jobs; j++) {
+        const int32_t *q = jobs + 3 * (size_t)j;
+        if (q[0] < 0 || q[0] >= n || q[1] < 0 || q[1] > q[2] || q[2] > n)
+            return fail(c, MP_ERR_ARG, "mp_dimer_cross: job %d is not {0 <= x < n, 0 <= y_lo <= y_hi <= n}", j);
+    }
+    if ((rc = ensure_dimer_tables(c, loss_hit, dg))) return rc;
+    const size_t total = (size_t)off[n];
+    Scratch sc(c);
+    uint8_t *d_codes = nullptr;
+    int32_t *d_off = nullptr, *d_hits = nullptr, *d_jobs = nullptr;
+    unsigned long long *d_n = nullptr;
+    if ((rc = sc.alloc(&d_codes, total)) || (rc = sc.alloc(&d_off, (size_t)n + 1)) || (rc = sc.alloc(&d_hits, (size_t)cap * 6)) ||
+        (rc = sc.alloc(&d_jobs, (size_t)n_jobs * 3)) || (rc = sc.alloc(&d_n, 1))) return rc;
+    HIPCK(c, hipMemcpyAsync(d_codes, codes, total, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(d_off, off, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(d_jobs, jobs, sizeof(int32_t) * 3 * (size_t)n_jobs, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream));
+    DimerArgs da{d_codes, d_off, n, 0, 0, c->dm_loss, c->dm_dg, dg_limit, (long long)cap, d_hits, d_n};
+    PrimRec<false> *d_prim = nullptr;                  // (function scope: Scratch frees through the variables' addresses)
+    PrimRec<true> *d_priml = nullptr;
+    if (longest > 32) {
+        if ((rc = sc.alloc(&d_priml, (size_t)n))) return rc;
+        hipLaunchKernelGGL(prim_kernel<true>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, d_codes, d_off, (int)n, d_priml);
+        hipLaunchKernelGGL(dimer_cross_kernel<true>, dim3((unsigned)n_jobs), dim3(kBlock), 0, c->stream, da, (const PrimRec<true> *)d_priml, (const int32_t *)d_jobs);
+    } else {
+        if ((rc = sc.alloc(&d_prim, (size_t)n))) return rc;
+        hipLaunchKernelGGL(prim_kernel<false>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, d_codes, d_off, (int)n, d_prim);
+        hipLaunchKernelGGL(dimer_cross_kernel<false>, dim3((unsigned)n_jobs), dim3(kBlock), 0, c->stream, da, (const PrimRec<false> *)d_prim, (const int32_t *)d_jobs);
+    }
+    HIPCK(c, hipGetLastError());
+    unsigned long long nh = 0;
+    HIPCK(c, hipMemcpyAsync(&nh, d_n, sizeof(nh), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    size_t ncopy = (size_t)std::min<unsigned long long>(nh, (unsigned long long)cap);
+    if (ncopy) HIPCK(c, hipMemcpy(hits, d_hits, sizeof(int32_t) * 6 * ncopy, hipMemcpyDeviceToHost));
+    *n_hits = (int64_t)nh;
     return MP_OK;
 }
 

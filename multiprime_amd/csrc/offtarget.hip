@@ -541,9 +541,343 @@ int offtarget_run(mp_ctx *c, const char *who, int32_t n_pat, const uint8_t *pat_
     return rc;
 }
 
+// ---- the class joins of the panel update (include/mprime_panel.h) ----------------------------------------------------------------------
+// Sites carry a class (0 core, 1 new); the site map has four segments of n_bases entries, segment = 2 * class + strand, so the compaction
+// leaves the sites ascending in (class, strand, sequence, position).  A join takes the forward segment of one class and the reverse
+// segment of another: the two slices are copied into one key array in join_device's layout and joined by the kernels above.
+constexpr int kJoinClasses = 3;
+constexpr int kJoinFwd[kJoinClasses] = {0, 2, 2};          // segment of the forward sites: core, new, new
+constexpr int kJoinRev[kJoinClasses] = {3, 1, 3};          // segment of the reverse sites: new, core, new
+
+struct OtClassSites {
+    struct State { unsigned hits; };
+    uint32_t *map;                    // [4][n_bases]: segment 2 * class + strand
+    const int64_t *roff;
+    long long n_bases;
+    const int32_t *read_class;        // [n_reads] 0 core, 1 new
+    unsigned long long *n_hits;
+    __device__ State begin() const { return {0u}; }
+    __device__ void hit(State &st, int row, long long p, int id, int strand) const {
+        atomicMax(map + (long long)(2 * read_class[id] + strand) * n_bases + roff[row] + p, (uint32_t)id + 1u);
+        st.hits++;
+    }
+    __device__ void end(State &st, int) const {
+        unsigned h = st.hits;
+        for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o);
+        if (__lane_id() == 0 && h) atomicAdd(n_hits, (unsigned long long)h);
+    }
+};
+
+// first site of every segment: bound[s] for s = 0 .. 4
+__global__ void segment_bounds_kernel(const long long *__restrict__ key, long long n_sites, long long n_bases, long long *__restrict__ bound) {
+    if (threadIdx.x <= 4) bound[threadIdx.x] = lower_bound(key, 0, n_sites, (long long)threadIdx.x * n_bases);
+}
+
+// the sites [f_lo, f_lo + n_f) and [r_lo, r_lo + n_r) of the compacted map as one join input: forward keys first, reverse keys at n_bases +
+__global__ __launch_bounds__(kBlock) void join_pick_kernel(const long long *__restrict__ key, const int32_t *__restrict__ primer, long long f_lo,
+                                                           long long n_f, long long f_sub, long long r_lo, long long n_r, long long r_sub,
+                                                           long long n_bases, long long *__restrict__ out_key, int32_t *__restrict__ out_primer) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_f + n_r) return;
+    if (i < n_f) { out_key[i] = key[f_lo + i] - f_sub; out_primer[i] = primer[f_lo + i]; }
+    else { out_key[i] = key[r_lo + i - n_f] - r_sub + n_bases; out_primer[i] = primer[r_lo + i - n_f]; }
+}
+
+// one join through join_device; its products, widened by the class column, are appended to out7 and its counts added to acc[1..6]
+int join_one_class(mp_ctx *c, const long long *d_key, const int32_t *d_primer, long long n_sites, const int64_t *d_roff, int n_rows,
+                   long long n_bases, const int32_t *d_row_key, int32_t size_lo, int32_t size_hi, int cls, std::vector<int32_t> &out7, int64_t *acc) {
+    int rc = join_device(c, d_key, d_primer, n_sites, d_roff, n_rows, n_bases, d_row_key, size_lo, size_hi);
+    if (rc != MP_OK) return rc;
+    const size_t n = (size_t)c->ot_n;
+    std::vector<int32_t> six(n * 6);
+    if (n) {
+        HIPCK(c, hipMemcpyAsync(six.data(), c->ot_out, sizeof(int32_t) * 6 * n, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+    }
+    out7.reserve(out7.size() + n * 7);
+    for (size_t i = 0; i < n; i++) {
+        out7.insert(out7.end(), six.begin() + 6 * i, six.begin() + 6 * i + 6);
+        out7.push_back(cls);
+    }
+    for (int i = 1; i < kOtCounts; i++) acc[i] += c->ot_counts[i];
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);          // the six-column products belong to no store
+    c->ot_n = 0;
+    return MP_OK;
+}
+
+int copy_out7(const std::vector<int32_t> &all, int64_t cap, int32_t *out, int64_t *n_out) {
+    const int64_t n = (int64_t)(all.size() / 7);
+    *n_out = n;
+    const int64_t k = std::min<int64_t>(cap, n);
+    if (k > 0) memcpy(out, all.data(), sizeof(int32_t) * 7 * (size_t)k);
+    return MP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mp_amplicon_join_classes(mp_ctx *c, int64_t n_sites, const int32_t *sites, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out,
+                             int64_t *n_out) {
+    if (!c) return MP_ERR_ARG;
+    if (n_sites < 0 || !n_out || cap < 0 || (cap && !out) || (n_sites && !sites)) return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: bad arguments");
+    HIPCK(c, hipSetDevice(c->dev));
+    const auto t0 = std::chrono::steady_clock::now();
+    *n_out = 0;
+    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);           // explicit sites replace whatever the resident screen kept
+    c->ot_n = 0;
+    c->ot_key.clear();
+    if (n_sites == 0) return MP_OK;
+    int32_t max_row = 0;
+    std::vector<long long> seg_key[4];
+    std::vector<int32_t> seg_read[4];
+    for (int64_t i = 0; i < n_sites; i++) {
+        const int32_t *s = sites + 5 * i;
+        if ((s[0] != 0 && s[0] != 1) || (s[1] != 0 && s[1] != 1) || s[2] < 0 || s[3] < 0)
+            return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: site %lld is not {0|1, 0|1, row >= 0, pos >= 0, read}", (long long)i);
+        if (s[2] >= (1 << 29)) return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: row %d of site %lld: at most 2^29 rows", s[2], (long long)i);
+        if (i) {
+            const int32_t *p = s - 5;
+            if (std::make_tuple(p[0], p[1], p[2], p[3]) >= std::make_tuple(s[0], s[1], s[2], s[3]))
+                return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: sites must ascend strictly in (class, strand, row, position) (site %lld)", (long long)i);
+        }
+        max_row = std::max(max_row, s[2]);
+        seg_key[2 * s[0] + s[1]].push_back(((long long)s[2] << 32) + s[3]);
+        seg_read[2 * s[0] + s[1]].push_back(s[4]);
+    }
+    const int n_rows = max_row + 1;
+    const long long n_bases = (long long)n_rows << 32;
+    std::vector<int32_t> row_key((size_t)n_rows);
+    std::vector<int64_t> roff((size_t)n_rows + 1);
+    for (int r = 0; r <= n_rows; r++) roff[(size_t)r] = (int64_t)r << 32;
+    for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;
+    long long *d_key = nullptr;
+    int32_t *d_primer = nullptr, *d_rkey = nullptr;
+    int64_t *d_roff = nullptr;
+    const size_t ns = (size_t)n_sites, nr = (size_t)n_rows;
+    auto cleanup = [&]() { dev_free(c, &d_key, ns); dev_free(c, &d_primer, ns); dev_free(c, &d_rkey, nr); dev_free(c, &d_roff, nr + 1); };
+    int rc;
+    if ((rc = dev_alloc(c, &d_key, ns)) || (rc = dev_alloc(c, &d_primer, ns)) || (rc = dev_alloc(c, &d_rkey, nr)) || (rc = dev_alloc(c, &d_roff, nr + 1))) {
+        cleanup(); return rc;
+    }
+    hipError_t e = hipMemcpyAsync(d_rkey, row_key.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "mp_amplicon_join_classes: %s", hipGetErrorString(e)); }
+    std::vector<int32_t> all;
+    int64_t acc[kOtCounts] = {0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < kJoinClasses && rc == MP_OK; k++) {
+        const auto &fk = seg_key[kJoinFwd[k]], &rk = seg_key[kJoinRev[k]];
+        if (fk.empty() || rk.empty()) continue;
+        std::vector<long long> key(fk);
+        std::vector<int32_t> primer(seg_read[kJoinFwd[k]]);
+        for (long long v : rk) key.push_back(n_bases + v);
+        primer.insert(primer.end(), seg_read[kJoinRev[k]].begin(), seg_read[kJoinRev[k]].end());
+        e = hipMemcpyAsync(d_key, key.data(), sizeof(long long) * key.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_primer, primer.data(), sizeof(int32_t) * primer.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { rc = fail(c, MP_ERR_DEVICE, "mp_amplicon_join_classes: %s", hipGetErrorString(e)); break; }
+        rc = join_one_class(c, d_key, d_primer, (long long)key.size(), d_roff, n_rows, n_bases, d_rkey, size_lo, size_hi, k, all, acc);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    cleanup();
+    if (rc != MP_OK) return rc;
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = acc[i];
+    rc = copy_out7(all, cap, out, n_out);
+    c->ot_ms[2] = c->ot_ms[3] = ms_since(t0);
+    return rc;
+}
+
+int mp_offtarget_classes(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_id,
+                         const int32_t *read_class, const int32_t *max_mm, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap,
+                         int32_t *out, int64_t *n_out) {
+    const char *who = "mp_offtarget_classes";
+    if (!c) return MP_ERR_ARG;
+    if (n_pat < 0 || !n_out || cap < 0 || (cap && !out) || (n_pat && (!pat_codes || !pat_off || !read_id || !read_class || !max_mm)) || term < 0)
+        return fail(c, MP_ERR_ARG, "%s: bad arguments", who);
+    HIPCK(c, hipSetDevice(c->dev));
+    const auto t0 = std::chrono::steady_clock::now();
+    *n_out = 0;
+    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
+    for (int32_t i = 0; i < n_pat; i++) {
+        const int len = pat_off[i + 1] - pat_off[i];
+        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
+        for (int j = 0; j < len; j++) {
+            const uint8_t m = pat_codes[pat_off[i] + j];
+            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
+        }
+        if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative mismatch budget", i);
+        if (read_class[i] != 0 && read_class[i] != 1) return fail(c, MP_ERR_ARG, "pattern %d has class %d (0 core, 1 new)", i, read_class[i]);
+    }
+    // the six-column products of the plain screen do not survive this call (join_device reuses their buffer)
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
+    c->ot_n = 0;
+    c->ot_key.clear();
+    if (c->sq_n == 0 || n_pat == 0) {
+        for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+        c->otc_out.clear();
+        c->otc_key.clear();
+        return MP_OK;
+    }
+    std::vector<uint8_t> key;
+    const int32_t head[4] = {n_pat, term, size_lo, size_hi};
+    put(key, head, 4);
+    put(key, pat_off, (size_t)n_pat + 1);
+    put(key, pat_codes + pat_off[0], (size_t)(pat_off[n_pat] - pat_off[0]));
+    put(key, read_id, (size_t)n_pat);
+    put(key, read_class, (size_t)n_pat);
+    put(key, max_mm, (size_t)n_pat);
+    if (!c->otc_key.empty() && key == c->otc_key) {         // a repeat of the last call: nothing is scanned again
+        int rc = copy_out7(c->otc_out, cap, out, n_out);
+        c->ot_ms[3] = ms_since(t0);
+        return rc;
+    }
+    c->otc_key.clear();
+    c->otc_out.clear();
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+    const long long n_bases = (long long)c->sq_total, n4 = 4 * n_bases;
+    const int n_rows = c->sq_n;
+    std::vector<int32_t> blk_row, blk_seg;
+    for (int32_t r = 0; r < n_rows; r++) {
+        const int64_t len = c->sq_roff_host[(size_t)r + 1] - c->sq_roff_host[(size_t)r];
+        for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
+    }
+    const size_t nb = std::max<size_t>(blk_row.size(), 1);
+    std::vector<int32_t> budgets(max_mm, max_mm + n_pat);
+    std::sort(budgets.begin(), budgets.end());
+    budgets.erase(std::unique(budgets.begin(), budgets.end()), budgets.end());
+    struct Table { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; };
+    std::vector<Table> tables;
+    for (int32_t b : budgets) {
+        std::vector<uint8_t> codes;
+        std::vector<int32_t> off{0}, ids;
+        int longest = 0;
+        for (int32_t i = 0; i < n_pat; i++) {
+            if (max_mm[i] != b) continue;
+            codes.insert(codes.end(), pat_codes + pat_off[i], pat_codes + pat_off[i + 1]);
+            off.push_back((int32_t)codes.size());
+            ids.push_back(i);
+            longest = std::max(longest, pat_off[i + 1] - pat_off[i]);
+        }
+        Table T{b, longest > 32, {}, 0};
+        auto fill = [&](auto &pats) {
+            kmm_patterns(off.size() - 1, codes.data(), off.data(), term, pats);
+            for (auto &P : pats) P.id = ids[(size_t)P.id];
+            T.n = (int)pats.size();
+            put(T.bytes, pats.data(), pats.size());
+        };
+        if (T.two) { std::vector<KmmPat<2>> p; fill(p); } else { std::vector<KmmPat<1>> p; fill(p); }
+        tables.push_back(std::move(T));
+    }
+    size_t pat_bytes = 1;
+    for (auto &T : tables) pat_bytes = std::max(pat_bytes, T.bytes.size());
+
+    uint32_t *map = nullptr;
+    int32_t *d_brow = nullptr, *d_bseg = nullptr, *d_rid = nullptr, *d_rcls = nullptr, *primer = nullptr, *d_rkey = nullptr, *jprimer = nullptr;
+    uint8_t *d_pats = nullptr;
+    unsigned long long *d_hits = nullptr;
+    long long *ccnt = nullptr, *cbase = nullptr, *skey = nullptr, *d_bound = nullptr, *jkey = nullptr;
+    const long long n_chunks = (n4 + kChunk - 1) / kChunk;
+    long long n_sites = 0;
+    size_t ns = 1;
+    auto cleanup = [&]() {
+        dev_free(c, &map, (size_t)n4); dev_free(c, &d_brow, nb); dev_free(c, &d_bseg, nb); dev_free(c, &d_rid, (size_t)n_pat);
+        dev_free(c, &d_rcls, (size_t)n_pat); dev_free(c, &d_pats, pat_bytes); dev_free(c, &d_hits, 1); dev_free(c, &ccnt, (size_t)n_chunks);
+        dev_free(c, &cbase, (size_t)n_chunks + 1); dev_free(c, &skey, ns); dev_free(c, &primer, ns); dev_free(c, &d_rkey, (size_t)n_rows);
+        dev_free(c, &d_bound, 5); dev_free(c, &jkey, ns); dev_free(c, &jprimer, ns);
+    };
+    int rc;
+    if ((rc = dev_alloc(c, &map, (size_t)n4)) || (rc = dev_alloc(c, &d_brow, nb)) || (rc = dev_alloc(c, &d_bseg, nb)) ||
+        (rc = dev_alloc(c, &d_rid, (size_t)n_pat)) || (rc = dev_alloc(c, &d_rcls, (size_t)n_pat)) || (rc = dev_alloc(c, &d_pats, pat_bytes)) ||
+        (rc = dev_alloc(c, &d_hits, 1)) || (rc = dev_alloc(c, &ccnt, (size_t)n_chunks)) || (rc = dev_alloc(c, &cbase, (size_t)n_chunks + 1)) ||
+        (rc = dev_alloc(c, &d_rkey, (size_t)n_rows)) || (rc = dev_alloc(c, &d_bound, 5))) {
+        cleanup(); return rc;
+    }
+    std::vector<int32_t> row_key((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;           // sequences in ascending store order
+    hipError_t e = hipMemsetAsync(map, 0, sizeof(uint32_t) * (size_t)n4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess && !blk_row.empty()) {
+        e = hipMemcpyAsync(d_brow, blk_row.data(), sizeof(int32_t) * blk_row.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_bseg, blk_seg.data(), sizeof(int32_t) * blk_seg.size(), hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rid, read_id, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rcls, read_class, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rkey, row_key.data(), sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
+    const auto t_scan = std::chrono::steady_clock::now();
+    OtClassSites sink{map, c->sq_roff, n_bases, d_rcls, d_hits};
+    for (auto &T : tables) {
+        if (blk_row.empty()) break;
+        e = hipMemcpyAsync(d_pats, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        if (T.two)
+            hipLaunchKernelGGL((kmm_kernel<2, true, OtClassSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
+                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
+                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats),
+                               T.n, (int)T.budget, sink);
+        else
+            hipLaunchKernelGGL((kmm_kernel<1, true, OtClassSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
+                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
+                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<1> *>(d_pats),
+                               T.n, (int)T.budget, sink);
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);          // (stage times on the host clock; the pattern tables may go now)
+    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s scan: %s", who, hipGetErrorString(e)); }
+    c->ot_ms[0] = ms_since(t_scan);
+    const auto t_red = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL(map_count_kernel, dim3(grid(n4, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n4, ccnt);
+    e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); cleanup(); return fail(c, MP_ERR_DEVICE, "%s reduce: %s", who, hipGetErrorString(e)); }
+    if ((rc = scan_i64(c, ccnt, n_chunks, cbase))) { (void)hipStreamSynchronize(c->stream); cleanup(); return rc; }
+    unsigned long long h_hits = 0;
+    e = hipMemcpyAsync(&n_sites, cbase + n_chunks, sizeof n_sites, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_hits, d_hits, sizeof h_hits, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s reduce: %s", who, hipGetErrorString(e)); }
+    ns = (size_t)std::max<long long>(n_sites, 1);
+    if ((rc = dev_alloc(c, &skey, ns)) || (rc = dev_alloc(c, &primer, ns)) || (rc = dev_alloc(c, &jkey, ns)) || (rc = dev_alloc(c, &jprimer, ns))) {
+        cleanup(); return rc;
+    }
+    long long bound[5] = {0, 0, 0, 0, 0};
+    hipLaunchKernelGGL(map_write_kernel, dim3(grid(n4, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n4, (const long long *)cbase,
+                       (const int32_t *)d_rid, skey, primer);
+    hipLaunchKernelGGL(segment_bounds_kernel, dim3(1), dim3(64), 0, c->stream, (const long long *)skey, n_sites, n_bases, d_bound);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(bound, d_bound, sizeof bound, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s reduce: %s", who, hipGetErrorString(e)); }
+    c->ot_ms[1] = ms_since(t_red);
+    const auto t_join = std::chrono::steady_clock::now();
+    std::vector<int32_t> all;
+    int64_t acc[kOtCounts] = {0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < kJoinClasses && rc == MP_OK; k++) {
+        const int fs = kJoinFwd[k], rs = kJoinRev[k];
+        const long long n_f = bound[fs + 1] - bound[fs], n_r = bound[rs + 1] - bound[rs];
+        if (n_f == 0 || n_r == 0) continue;
+        hipLaunchKernelGGL(join_pick_kernel, dim3(grid(n_f + n_r, kBlock)), dim3(kBlock), 0, c->stream, (const long long *)skey, (const int32_t *)primer,
+                           bound[fs], n_f, (long long)fs * n_bases, bound[rs], n_r, (long long)rs * n_bases, n_bases, jkey, jprimer);
+        e = hipGetLastError();
+        if (e != hipSuccess) { rc = fail(c, MP_ERR_DEVICE, "%s join: %s", who, hipGetErrorString(e)); break; }
+        rc = join_one_class(c, jkey, jprimer, n_f + n_r, c->sq_roff, n_rows, n_bases, d_rkey, size_lo, size_hi, k, all, acc);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    cleanup();
+    if (rc != MP_OK) return rc;
+    c->ot_ms[2] = ms_since(t_join);
+    acc[0] = (int64_t)h_hits;
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = acc[i];
+    c->otc_out = std::move(all);
+    c->otc_key = std::move(key);
+    rc = copy_out7(c->otc_out, cap, out, n_out);
+    c->ot_ms[3] = ms_since(t0);
+    return rc;
+}
 
 int mp_offtarget_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
                           const int32_t *max_mm, int32_t term, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {

@@ -132,6 +132,8 @@ void free_seq(mp_ctx *c) {
     dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);      // products of mp_offtarget_resident belong to the store they came from
     c->ot_n = 0;
     c->ot_key.clear();
+    c->otc_out.clear();
+    c->otc_key.clear();
 }
 }  // namespace mp
 
