@@ -416,7 +416,8 @@ __device__ inline bool pair_search(const PrimRec<LONG> &X, const PrimRec<LONG> &
 // All pairs of n primers: workgroup = one primer x (its record is wave-uniform), threads stride over the partners y the mode asks
 // for.  Every partner goes through the bit-plane filter; the few that pass are queued in LDS and searched 256 at a time, so the
 // search runs with full waves instead of one or two lanes of every wave.  Hits are collected in LDS and appended to the output
-// with ONE device atomic per flush (~n atomics on the shared counter per launch instead of one per hit).
+// with ONE device atomic per flush (~n atomics on the shared counter per launch instead of one per hit).  One extra barrier per
+// stride of 256 partners keeps the "drain or not" decision the same in every wave (see dimer_cross_kernel below for the sizes).
 constexpr int kHitBuf = 1024, kQueue = 2 * kBlock;
 template <bool LONG>
 __global__ __launch_bounds__(kBlock) void dimer_rows_kernel(const DimerArgs A, const PrimRec<LONG> *__restrict__ prim) {
@@ -448,7 +449,8 @@ __global__ __launch_bounds__(kBlock) void dimer_rows_kernel(const DimerArgs A, c
             }
         }
         __syncthreads();
-        const int queued = s_q;
+        const int queued = s_q;                                     // read between TWO barriers, as in dimer_cross_kernel: no wave enqueues for the
+        __syncthreads();                                            // next stride while another still reads, so all waves take the same branch
         if (queued >= kBlock || last) {                             // (queued < 2 * kBlock: at most kBlock - 1 were left, kBlock came)
             for (int i = threadIdx.x; i < queued; i += kBlock) {
                 const int yq = s_qy[i];
