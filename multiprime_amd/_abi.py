@@ -223,6 +223,17 @@ PANEL_SYMBOLS = [
     ("mp_offtarget_classes", C.c_int, [_p, C.c_int32, _p, _p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
 ]
 ONT_Q_ROWS, ONT_Q_COLS = 129, 65    # MP_ONT_Q_ROWS, MP_ONT_Q_COLS
+# include/mprime_setscreen.h: per-pair product counts for the off-target-aware set cover (csrc/setscreen.hip) — exported by
+# libmprime_hip.so only; the checker of these calls is the plain restatement of the rule in tests/setscreen_ref.py
+SETSCREEN_SYMBOLS = [
+    ("mp_setscreen_begin", C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("mp_setscreen_add", C.c_int, [_p, C.c_int32, _p, _p, _p, C.c_int64, _p, C.POINTER(C.c_int64)]),
+    ("mp_setscreen_site_counts", C.c_int, [_p, C.c_int32, C.c_int32, _p, _p]),
+    ("mp_setscreen_stats", C.c_int, [_p, _p, _p]),
+    ("mp_setscreen_end", C.c_int, [_p]),
+    ("mp_setscreen_join", C.c_int, [_p, C.c_int64, _p, C.c_int32, C.c_int32, C.c_int64, _p, C.POINTER(C.c_int64)]),
+]
+SETSCREEN_BIN = 1024                # MP_SETSCREEN_BIN
 
 
 def prefer_staged_copies():
@@ -343,7 +354,10 @@ class Library:
         self.panel = all(hasattr(self.dll, name) for name, _, _ in PANEL_SYMBOLS)
         if self.backend == "hip" and not self.panel:
             raise MprimeError(-2, f"{path} lacks the panel-update entry points of include/mprime_panel.h: rebuild it")
-        for name, res, args in ((PANEL_SYMBOLS if self.panel else []) + (OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
+        self.setscreen = all(hasattr(self.dll, name) for name, _, _ in SETSCREEN_SYMBOLS)
+        if self.backend == "hip" and not self.setscreen:
+            raise MprimeError(-2, f"{path} lacks the set-screen entry points of include/mprime_setscreen.h: rebuild it")
+        for name, res, args in ((PANEL_SYMBOLS if self.panel else []) + (SETSCREEN_SYMBOLS if self.setscreen else []) + (OFFTARGET_SYMBOLS if self.offtarget else []) + (GAP_SYMBOLS if self.gapscan else []) +
                                 (ANCHOR_SYMBOLS if self.anchor else []) + (CLUSTER_SYMBOLS if self.cluster else []) +
                                 (STAR_SYMBOLS if self.star else []) + (ANI_SYMBOLS if self.ani else []) +
                                 (DEGE_SYMBOLS if self.dege else []) + (ONT_SYMBOLS if self.ont else []) +
@@ -963,6 +977,76 @@ class Context:
                                                  int(term), int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
             if n.value <= cap:
                 return out[: n.value]
+            cap = int(n.value)
+
+    # include/mprime_setscreen.h
+    def _need_setscreen(self):
+        if not self.lib.setscreen:
+            raise MprimeError(-2, f"{self.lib.path} does not serve include/mprime_setscreen.h (libmprime_hip.so does)")
+
+    @staticmethod
+    def _sorted_triples(t):
+        return t[np.lexsort((t[:, 1], t[:, 0]))] if len(t) else t
+
+    def setscreen_begin(self, size_lo: int, size_hi: int, max_mismatch: int, term: int):
+        """Open the set screen of this context on the store of seq_load: products with size_lo < length < size_hi."""
+        self._need_setscreen()
+        self._ck(self.d.mp_setscreen_begin(self.h, int(size_lo), int(size_hi), int(max_mismatch), int(term)))
+
+    def setscreen_add_raw(self, pat_codes, pat_off, read_primer, cap: int):
+        """One mp_setscreen_add call as it is: (the first min(cap, n) triples in arrival order, n)."""
+        self._need_setscreen()
+        pat_codes = np.ascontiguousarray(pat_codes, dtype=np.uint8)
+        pat_off = np.ascontiguousarray(pat_off, dtype=np.int32)
+        read_primer = np.ascontiguousarray(read_primer, dtype=np.int32)
+        out = np.empty((max(cap, 1), 3), np.int64)
+        n = C.c_int64(0)
+        self._ck(self.d.mp_setscreen_add(self.h, len(pat_off) - 1, _ptr(pat_codes), _ptr(pat_off), _ptr(read_primer), cap,
+                                         _ptr(out) if cap else None, C.byref(n)))
+        return out[: min(cap, n.value)], int(n.value)
+
+    def setscreen_add(self, pat_codes, pat_off, read_primer, cap: int = 1 << 16, with_stats: bool = False):
+        """Screen the reads of new primers (read_primer: global primer ids, non-decreasing, above every earlier id).  Triples [n][3]
+        int64 = (A, B, products(A -> B)) of the ordered pairs with a new primer and a product, sorted by (A, B).  A result larger than
+        `cap` is fetched again with the exact size: the library kept it, nothing is scanned twice.  with_stats: (triples,
+        setscreen_stats() of the call that scanned — the fetch that follows it reports zeros)."""
+        t, n = self.setscreen_add_raw(pat_codes, pat_off, read_primer, cap)
+        stats = self.setscreen_stats() if with_stats else None
+        if n > cap:
+            t, n = self.setscreen_add_raw(pat_codes, pat_off, read_primer, n)
+        t = self._sorted_triples(t)
+        return (t, stats) if with_stats else t
+
+    def setscreen_site_counts(self, first: int, n: int):
+        """(forward, reverse) int64 [n]: the de-duplicated sites of primers first .. first + n - 1."""
+        self._need_setscreen()
+        f, r = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        self._ck(self.d.mp_setscreen_site_counts(self.h, int(first), int(n), _ptr(f), _ptr(r)))
+        return f[:n], r[:n]
+
+    def setscreen_stats(self):
+        """Of the last setscreen_add / setscreen_join: ({scan, bin, join, call}_ms, counts)."""
+        self._need_setscreen()
+        ms, counts = np.zeros(4, np.float64), np.zeros(8, np.int64)
+        self._ck(self.d.mp_setscreen_stats(self.h, _ptr(ms), _ptr(counts)))
+        return (dict(zip(("scan_ms", "bin_ms", "join_ms", "call_ms"), ms.tolist())),
+                dict(zip(("scan_launches", "list_regrows", "table_regrows", "forward_sites", "reverse_sites", "pairs", "products", "adds"),
+                         counts.tolist())))
+
+    def setscreen_end(self):
+        self._need_setscreen()
+        self._ck(self.d.mp_setscreen_end(self.h))
+
+    def setscreen_join(self, sites, size_lo: int, size_hi: int, cap: int = 1 << 16) -> np.ndarray:
+        """The join alone: sites [n][4] = (strand, row, position, primer id), strictly ascending; triples as setscreen_add."""
+        self._need_setscreen()
+        sites = np.ascontiguousarray(sites, dtype=np.int32).reshape(-1, 4)
+        while True:
+            out = np.empty((max(cap, 1), 3), np.int64)
+            n = C.c_int64(0)
+            self._ck(self.d.mp_setscreen_join(self.h, len(sites), _ptr(sites), int(size_lo), int(size_hi), cap, _ptr(out), C.byref(n)))
+            if n.value <= cap:
+                return self._sorted_triples(out[: n.value])
             cap = int(n.value)
 
     # include/mprime_anchor.h

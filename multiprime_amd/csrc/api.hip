@@ -307,6 +307,7 @@ void mp_destroy(mp_ctx *c) {
     free_comm(c);
     free_msa(c);
     free_seq(c);
+    free_setscreen(c, false);
     free_anchor(c);
     free_cluster(c);
     free_star(c);

@@ -54,6 +54,7 @@ struct ChainItem {
 
 struct SlideBand;
 struct DegeState;
+struct SetScreen;
 
 // up to 16 * NQ symbol codes, one nibble each (position j = nibble j & 15 of word j >> 4).  NQ = 2: the k-mers of 32-bit window
 // words (the code of rounds 1-3, two named halves); NQ = 4: primers of 32..63 bases — the word index is a run-time value there, taken
@@ -342,6 +343,11 @@ struct mp_ctx {
     int32_t ont_n = 0, ont_max_len = 0;      // keys resident, the longest of them
     double ont_ms = 0;
     int64_t ont_counts[2] = {0, 0};
+    // off-target-aware set selection (setscreen.hip, include/mprime_setscreen.h): the open set screen (site list, pair table, kept triples;
+    // free_seq leaves it open but stale), and the times / counts of the last mp_setscreen_add / mp_setscreen_join
+    mp::SetScreen *ss = nullptr;
+    double ss_ms[4] = {0, 0, 0, 0};
+    int64_t ss_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run
@@ -456,6 +462,7 @@ void free_star(mp_ctx *c);       // star.hip
 void free_ani(mp_ctx *c);        // ani.hip
 void free_dege(mp_ctx *c);       // dege.hip
 void free_ont(mp_ctx *c);        // ont.hip
+void free_setscreen(mp_ctx *c, bool keep_stale);     // setscreen.hip (keep_stale: the store goes, the screen stays open and refuses adds)
 void free_windows(mp_ctx *c);
 void free_msa(mp_ctx *c);
 // per-translation-unit device constants (called by mp_create on the context's device)

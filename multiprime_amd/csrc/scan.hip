@@ -134,6 +134,7 @@ void free_seq(mp_ctx *c) {
     c->ot_key.clear();
     c->otc_out.clear();
     c->otc_key.clear();
+    free_setscreen(c, true);                           // a set screen belongs to the store it was opened on
 }
 }  // namespace mp
 

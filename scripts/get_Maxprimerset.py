@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's scripts/get_Maxprimerset.py (same flags -i -a -s -m -o, same output
-files incl. sort.<input> and <out>.next.xls); the dimer examinations run on an MI355X."""
+files incl. sort.<input> and <out>.next.xls); the dimer examinations run on an MI355X.  With -r <background.fa>
+(-p -d --seedmms --max-offtarget --cross-only --lookahead) a pair must also amplify nothing on the
+background, alone or with the primers already selected: <out>.offtarget.tsv and <out>.offtarget.set.tsv."""
 import os
 import sys
 

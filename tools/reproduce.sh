@@ -227,5 +227,10 @@ ont)             # profiles/ont.txt: reads to primers on a synthetic run (200000
   timeout -k 10 600 python tools/ont_bench.py 2>&1 | tee $O/ont.txt &&
   (echo "# MP_ONT_PRUNE=0"; MP_ONT_PRUNE=0 timeout -k 10 600 python tools/ont_bench.py --sample 20) 2>&1 | tee -a $O/ont.txt &&
   (echo "# MP_ONT_WORD=64"; MP_ONT_WORD=64 timeout -k 10 600 python tools/ont_bench.py --sample 20) 2>&1 | tee -a $O/ont.txt ;;
+setscreen)       # profiles/setscreen.txt: get_Maxprimerset -r on a synthetic 10^8-base background, 200 clusters x 8 pairs: device ms of scan / bin / join per add, run() wall with and without -r, the Python model on a 10^6-base slice scaled linearly
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_setscreen_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 600 python tools/setscreen_bench.py 2>&1 | tee $O/setscreen.txt &&
+  (echo "# --seedmms 0"; timeout -k 10 600 python tools/setscreen_bench.py --seedmms 0 --model-bases 0) 2>&1 | tee -a $O/setscreen.txt ;;
 *) echo "unknown target $T"; exit 2 ;;
 esac
