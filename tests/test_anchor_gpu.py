@@ -11,7 +11,7 @@ import pytest
 
 import anchor_cases as cases
 from conftest import REPO
-from multiprime_amd._abi import MprimeError
+from multiprime_amd._abi import ANCHOR_MAX_LEN, MprimeError
 from multiprime_amd.anchor import AnchoredAlignment
 from multiprime_amd.synth import synth_block, to_fasta
 
@@ -71,6 +71,23 @@ def test_results_do_not_depend_on_the_batch(n_queries, hip_lib, truth, monkeypat
         rows, meta, ops = ctx.anchor_align(*pack(g["queries"][:n_queries]))
         assert ops is None and [r.tobytes().decode() for r in rows] == [w["row"] for w in want[:n_queries]]
         assert meta[:, :8].tolist() == [[w[k] for k in FIELDS] for w in want[:n_queries]]
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_two_queries_at_the_length_limit(hip_lib, monkeypatch):
+    """An anchor of ANCHOR_MAX_LEN bases on identity columns, a copy with substitutions and a fragment with three inserted bases: one wave
+    per workgroup in the sweep and a vote histogram beyond 64 KiB.  The expectation comes from the planted homology
+    (star_edge_cases.limit_case; tests/test_star.py holds the yardstick to it at 3000 bases)."""
+    from star_edge_cases import limit_case
+    monkeypatch.delenv("MP_ANCHOR_BATCH", raising=False)
+    case = limit_case(ANCHOR_MAX_LEN)
+    g = dict(anchor=case["anchor"], col=list(range(ANCHOR_MAX_LEN)), width=ANCHOR_MAX_LEN, params={}, queries=case["records"][1:])
+    ctx = hip_lib.context(0)
+    try:
+        same(device(ctx, g), case["anchored"], "length limit")
+        assert ctx.anchor_stats()[1]["batches"] == 1
     finally:
         ctx.close()
 

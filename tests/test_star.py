@@ -1,9 +1,12 @@
 """The yardstick of the star alignment (tests/star_ref.py, the rule of include/mprime_star.h) checked on its own: what every case of
 tests/star_cases.py is meant to provoke does happen, every row is lossless, and a planted family comes back with its planted homology.
-No device is involved."""
+Then the same for the cases of tests/star_edge_cases.py, which take the device's kernels past one tile: the bands the records end at and
+where the flagged ones stand, the widths, the slots that carry insertions, the unplaced records at the tile boundaries, and the
+length-limit case against its planted expectation.  No device is involved."""
 import pytest
 
 import star_cases as cases
+import star_edge_cases as edges
 import star_ref as ref
 from anchor_ref import anchor_of
 
@@ -161,3 +164,115 @@ def test_refusals():
     with pytest.raises(ValueError):
         ref.star(["A" * (ref.MAX_LEN + 1)])
     assert ref.clean("ac-g.T") == "ACGT" and ref.centre_of(["AC", "ACG", "TTT"]) == 1
+
+
+# ---- the edge cases of tests/star_edge_cases.py: each provokes on the yardstick what tests/test_star_edges.py runs it for -------------------
+def ceil8(record):
+    return (len(record) + 7) // 8
+
+
+@pytest.mark.parametrize("n_records", edges.TINY_SIZES)
+def test_many_tiny_records_flag_fixed_positions_and_end_at_four_bands(n_records):
+    g = edges.many_tiny(n_records)
+    rnd, plan, runs = edges.yardstick_round(g), g["plan"], g["runs"]
+    records, bands = cases.cleaned(g), [m["band"] for m in rnd["meta"]]
+    assert len(records) == n_records and g["params"]["band"] == 4 and plan["per"] == {256: 1, 257: 1, 1024: 1, 1025: 2, 2049: 3}[n_records]
+    assert len(records[0]) == 48 and all(20 <= len(r) <= 60 for r in records[1:])
+    # every record ends at the band its run was chosen for; the strangers are unplaced and nothing else is
+    for q in range(n_records):
+        if q in plan["strangers"]:
+            assert not rnd["placed"][q] and set(records[q]) <= set("AG"), q
+        else:
+            assert bands[q] == edges.TINY_BAND_OF_RUN[runs[q]] if q in runs else bands[q] == 4, q
+            assert rnd["placed"][q] and rnd["meta"][q]["status"] == 0 and rnd["meta"][q]["n_ins"] == runs.get(q, 0), q
+    per_band = {W: sum(1 for q, b in enumerate(bands) if b == W and q not in plan["strangers"]) for W in (4, 8, 16, 32)}
+    assert per_band == {W: sum(1 for q in range(n_records) if q not in plan["strangers"] and edges.TINY_BAND_OF_RUN[runs.get(q, 3)] == W)
+                        for W in (4, 8, 16, 32)}
+    assert all(per_band[W] >= 5 for W in (8, 16, 32)) and per_band[4] > n_records // 2
+    assert sum(1 for q in runs if runs[q] == 3) >= 3 and sum(1 for x in rnd["ins"] if x) >= 10
+    # the flagged records where the flag scan's slices meet: 1..4, around the first record of three threads, the last records, one whole slice
+    per = plan["per"]
+    flagged = {q for q, b in enumerate(bands) if b > 4}
+    assert plan["flagged"] <= flagged and {1, 2, 3, 4} <= flagged and set(plan["full"]) <= flagged and len(plan["full"]) == per
+    assert all({per * t - 1, per * t, per * t + 1} <= flagged for t in plan["threads"])
+    assert {n_records - 3, n_records - 2, n_records - 1} - plan["strangers"] <= flagged and len(runs) > n_records // 10
+    if n_records >= 1024:
+        quiet = plan["quiet"]
+        assert len(quiet) == 200 * per and quiet[0] % per == 0 and not flagged & set(quiet)
+    # a profile workgroup (256 records) and a count workgroup (1024) start and end on an unplaced record
+    assert {q for q in (255, 256, 1023, 1024) if q < n_records} <= plan["strangers"]
+    if n_records >= 1024:
+        # a count lane reads every fourth row of the first 1024: one of them sees 256 gaps in an inserted column
+        lanes = [rl for rl in range(4) if all(rnd["placed"][r] for r in range(rl, 1024, 4))]
+        assert any(all(rnd["rows"][r][c] == "-" for r in range(rl, 1024, 4)) for rl in lanes for c in range(rnd["width"]))
+
+
+def test_rows_narrower_than_sixteen_bytes():
+    g = edges.one_letter()
+    rnd = edges.yardstick_round(g)
+    assert rnd["width"] == 1 and rnd["ins"] == [0, 0] and len(g["records"]) == 1030
+    assert [q for q, ok in enumerate(rnd["placed"]) if not ok] == [1024] and rnd["counts"] == [[1029, 0, 0, 0, 0, 0]]
+    g = edges.short_rows()
+    rnd, records = edges.yardstick_round(g), g["records"]
+    assert rnd["width"] == 7 and rnd["ins"] == [2, 0, 0, 0, 0, 0] and sorted({len(r) for r in records}) == [1, 2, 3, 4, 5]
+    assert rnd["rows"][records.index("ACG")] == "--ACG--" and rnd["rows"][records.index("GGACG")] == "GGACG--"
+    q = records.index("TTTTT")
+    assert not rnd["placed"][q] and rnd["placed"].count(False) == 1 and 0 < q < len(records) - 1 and 16 // 7 >= 2       # a lane spans three rows
+    g = edges.width15()
+    rnd = edges.yardstick_round(g)
+    assert rnd["width"] == 15 and rnd["ins"][0] == 2 and sum(rnd["ins"]) == 2 and (len(g["records"]) * 15) % 16
+    assert any(not rnd["placed"][q] and rnd["placed"][q - 1] and rnd["placed"][q + 1] for q in range(1, len(g["records"]) - 1))
+    assert rnd["placed"][0] and rnd["placed"][-1]
+
+
+@pytest.fixture(scope="module")
+def long_truth():
+    return {g["name"]: (g, edges.yardstick_round(g)) for g in edges.long_groups()}
+
+
+@pytest.mark.parametrize("n", edges.LONG_SIZES)
+def test_long_anchors_carry_insertions_where_the_tiles_meet(long_truth, n):
+    g, rnd = long_truth[f"long{n}"]
+    records, plan, per = cases.cleaned(g), g["plan"], g["per"]
+    assert len(records[0]) == n and per == (n + 1 + 1023) // 1024 == {1023: 1, 1024: 2, 2047: 2, 2048: 3, 2100: 3}[n]
+    assert {j: x for j, x in enumerate(rnd["ins"]) if x} == plan and all(rnd["placed"]) and all(m["band"] == 32 for m in rnd["meta"])
+    assert {0, n} | {j for j in (1023, 1024, 2047, 2048) if j <= n} <= set(plan) and len(plan) >= 12 + 2
+    # slices of the column scan with an insertion in their first and in their last slot
+    assert len(g["threads"]) >= 6 and all(rnd["ins"][per * t] and rnd["ins"][per * t + per - 1] for t in g["threads"])
+    assert rnd["width"] == n + sum(plan.values()) and rnd["rows"][1].startswith(records[1][:plan[0]])
+    assert rnd["rows"][-1].endswith(records[-1][-plan[n]:]) and rnd["rows"][0].endswith("-" * plan[n])
+    for a, b in zip(records, records[1:]):
+        assert a != b and ceil8(a) != ceil8(b)
+    assert all(1 <= len(h) <= 2 for h in g["held"]) and all(150 <= len(r) <= 400 for r in records[1:])
+
+
+def test_widths_1024_and_1025(long_truth):
+    for width in (1024, 1025):
+        g, rnd = long_truth[f"width{width}"]
+        assert len(g["anchor"]) == 1000 and rnd["width"] == width and {j: x for j, x in enumerate(rnd["ins"]) if x} == g["plan"]
+        assert rnd["ins"][0] == 3 and rnd["ins"][1000] == 3 and all(rnd["placed"])
+
+
+def test_every_record_of_the_chunked_list_is_aligned_again():
+    g = edges.chunked_list()
+    rnd, records = edges.yardstick_round(g), cases.cleaned(g)
+    assert len(records) == 45 and ref.centre_of(records) == 0 and records[0] == g["anchor"] and g["params"]["band"] == 32
+    assert [m["band"] for m in rnd["meta"]] == [{0: 32, 1: 64, 2: 128}[k] for k in g["kinds"]]
+    assert g["kinds"].count(1) == 29 and g["kinds"].count(2) == 15 and all(m["status"] == 0 for m in rnd["meta"])
+    assert len(set(records)) == 45 and all(ceil8(a) != ceil8(b) for a, b in zip(records, records[1:]))
+    assert all(m["n_del"] == {0: 0, 1: 40, 2: 70}[k] for m, k in zip(rnd["meta"], g["kinds"]))
+    # at four diagonals per lane (W = 64) the list takes more words than the whole batch at two (W = 32)
+    assert edges.flagged_words(g, rnd, 0, 45, 4) > sum(ceil8(r) * 128 for r in records)
+
+
+def test_the_length_limit_case_is_what_the_rule_gives():
+    case = edges.limit_case(3000)
+    anchor, records = case["anchor"], case["records"]
+    assert [len(r) for r in records] == [3000, 3000, case["b"] - 100 + 3] and case["a"] - 100 > case["b"] - case["a"] and case["substitutions"] > 40
+    rnd = ref.star_round(records, anchor)
+    for key in ("rows", "meta", "ins", "width", "counts", "placed"):
+        assert rnd[key] == case["star"][key], key
+    from anchor_ref import align
+    for q, want in zip(records[1:], case["anchored"]):
+        got = align(q, anchor, list(range(3000)), 3000)
+        assert {k: got[k] for k in want} == want
