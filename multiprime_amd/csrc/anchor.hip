@@ -38,10 +38,6 @@ __global__ __launch_bounds__(256) void anchor_emit_kernel(const uint8_t *__restr
         for (int x = 0; x < cnt; x++) rows[b0 + x] = (uint8_t)(w[x >> 2] >> (8 * (x & 3)));
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 void free_anchor(mp_ctx *c) {

@@ -268,10 +268,6 @@ __global__ __launch_bounds__(256) void cluster_dp_kernel(const uint8_t *__restri
     }
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 long long env_cap(const char *name, long long dflt) {
     if (const char *s = getenv(name)) { const long long v = atoll(s); if (v > 0) return v; }
     return dflt;

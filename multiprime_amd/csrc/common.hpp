@@ -426,6 +426,60 @@ void dev_free(mp_ctx *c, T **p, size_t n) {
     }
 }
 
+// HIPCK where host arrays of the call may still have copies in flight: the stream is waited for before the return lets them leave scope
+#define HIPCK_WAIT(c, call)                                                                              \
+    do {                                                                                                 \
+        hipError_t e_ = (call);                                                                          \
+        if (e_ != hipSuccess) {                                                                          \
+            (void)hipStreamSynchronize((c)->stream);                                                     \
+            return fail((c), MP_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_));                    \
+        }                                                                                                \
+    } while (0)
+
+// A device block released with its scope, or earlier by release() (the pool orders a released block on the stream: whatever was
+// enqueued on the context's stream before the release may still use it).  Copies and fills go to the context's stream.
+template <class T> struct DevBuf {
+    mp_ctx *c;
+    T *p = nullptr;
+    size_t n = 0;
+    explicit DevBuf(mp_ctx *ctx) : c(ctx) {}
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    int alloc(size_t k) { release(); n = k ? k : 1; return dev_alloc(c, &p, n); }
+    void release() { dev_free(c, &p, n); }
+    hipError_t upload(const T *src, size_t k) { return k ? hipMemcpyAsync(p, src, sizeof(T) * k, hipMemcpyHostToDevice, c->stream) : hipSuccess; }
+    hipError_t zero() { return hipMemsetAsync(p, 0, sizeof(T) * n, c->stream); }
+    ~DevBuf() { release(); }
+};
+
+// Device time of one stage on the context's stream, added to *ms when it is read.  A clock that cannot get its events reads nothing.
+struct StageClock {
+    hipEvent_t a = nullptr, b = nullptr;
+    void begin(mp_ctx *c) {
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, c->stream) != hipSuccess) drop();
+    }
+    void end(mp_ctx *c) { if (a && b && hipEventRecord(b, c->stream) != hipSuccess) drop(); }
+    void read(double *ms) {                  // waits for the stage's end
+        float x = 0;
+        if (a && b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&x, a, b) == hipSuccess) *ms += x;
+        drop();
+    }
+    void drop() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); a = b = nullptr; (void)hipGetLastError(); }
+    ~StageClock() { drop(); }
+};
+
+inline unsigned grid(long long n, long long per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
+
+// the bytes of p[0 .. n) appended to k (the key of a kept result: the arguments that made it)
+template <class T> void put(std::vector<uint8_t> &k, const T *p, size_t n) {
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
+    k.insert(k.end(), b, b + sizeof(T) * n);
+}
+
+inline double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
 // Several arrays set to a 32-bit pattern by ONE kernel launch (a stage's counters, cursors and tables used to cost one runtime fill
 // dispatch each, ~6 us apiece).  Sizes in bytes, multiples of 4; pointers from hipMalloc.  api.hip
 struct FillSeg { void *p; size_t bytes; uint32_t value; };

@@ -1,6 +1,10 @@
-// kmm.hpp — the k-mismatch primer-site scan kernel of scan.hip (mp_kmm_scan) and offtarget.hip (mp_offtarget_resident): one
-// matching rule and one pattern table for both.  What a hit does is the Sink's business: scan.hip appends it to a hit list,
-// offtarget.hip folds it into a per-position site map.
+// kmm.hpp — the k-mismatch primer-site scan: its kernels and the host code that drives them, one matching rule, one pattern table
+// and one launch for its four users.  What a hit does is the Sink's business:
+//   scan.hip       validation (mp_kmm_scan, mp_kmm_scan_resident, mp_kmm_gap_scan_resident): KmmAppend, every hit into a hit list
+//   offtarget.hip  the off-target screen (mp_offtarget_resident, mp_offtarget_gap_resident): OtSites, a site map of two segments
+//   offtarget.hip  the panel update's class screen (mp_offtarget_classes): OtClassSites, a site map of four segments
+//   setscreen.hip  the set screen (mp_setscreen_add): SsAppend, de-duplicated site records into the screen's list
+// The driver at the end of this file: kmm_check_patterns, KmmBlocks (the workgroups of a scan), kmm_table / kmm_tables, kmm_launch.
 #pragma once
 
 #include "common.hpp"
@@ -307,6 +311,152 @@ void kmm_patterns(int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_of
             pats.push_back(P);
         }
     }
+}
+
+// ---- the driver: what every scan does on the host ------------------------------------------------------------------------------------
+// the one pattern check: a length the tables hold, concrete bases only; then `also(i)`, what the caller asks of pattern i beside that
+// (patterns are checked in order, so the first pattern at fault is the one reported)
+template <class Also>
+int kmm_check_patterns(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, Also also) {
+    for (int32_t i = 0; i < n_pat; i++) {
+        const int len = pat_off[i + 1] - pat_off[i];
+        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
+        for (int j = 0; j < len; j++) {
+            const uint8_t m = pat_codes[pat_off[i] + j];
+            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
+        }
+        if (int rc = also(i)) return rc;
+    }
+    return MP_OK;
+}
+inline int kmm_check_patterns(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off) {
+    return kmm_check_patterns(c, n_pat, pat_codes, pat_off, [](int32_t) { return MP_OK; });
+}
+
+// The workgroups of a scan: one per (record, segment of kSeg starts), built on the host per call and uploaded.  The host lists live as
+// long as the object: upload() is covered by the next synchronisation of the stream, which comes before the object goes.
+struct KmmBlocks {
+    std::vector<int32_t> row, seg;
+    DevBuf<int32_t> d_row, d_seg;
+    size_t n = 0;
+    explicit KmmBlocks(mp_ctx *c) : d_row(c), d_seg(c) {}
+    size_t size() const { return n; }
+    void drop_host() { std::vector<int32_t>().swap(row); std::vector<int32_t>().swap(seg); }      // after the wait that covers upload()
+    int build(const int64_t *roff_host, int32_t n_rows) {
+        for (int32_t r = 0; r < n_rows; r++) {
+            const int64_t len = roff_host[r + 1] - roff_host[r];
+            if (len < 0 || len > 0x7fffffffLL) return fail(d_row.c, MP_ERR_ARG, "sequence %d has bad length", r);
+            for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { row.push_back(r); seg.push_back((int32_t)sgm); }
+        }
+        n = row.size();
+        int rc;
+        if ((rc = d_row.alloc(n)) || (rc = d_seg.alloc(n))) return rc;
+        return MP_OK;
+    }
+    hipError_t upload() {
+        const hipError_t e = d_row.upload(row.data(), row.size());
+        return e == hipSuccess ? d_seg.upload(seg.data(), seg.size()) : e;
+    }
+    void release() { d_row.release(); d_seg.release(); }
+};
+
+// One launch's pattern table: `n` entries of KmmPat<two ? 2 : 1> in `bytes`.  gaps > 0: kmm_gap_kernel with the penalty ceiling `budget`
+// and gaps of up to `gaps` bases; else kmm_kernel with `budget` mismatches.
+struct KmmTable { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; int32_t gaps; };
+
+// the table of the patterns idx[] in that order, both strands each; an entry's id is id_of[i] (null: i) of its pattern i; two words
+// per pattern as soon as one of them has more than 32 bases
+inline KmmTable kmm_table(const std::vector<int32_t> &idx, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *id_of, int32_t term) {
+    std::vector<uint8_t> codes;
+    std::vector<int32_t> off{0};
+    int longest = 0;
+    for (int32_t i : idx) {
+        codes.insert(codes.end(), pat_codes + pat_off[i], pat_codes + pat_off[i + 1]);
+        off.push_back((int32_t)codes.size());
+        longest = std::max(longest, pat_off[i + 1] - pat_off[i]);
+    }
+    KmmTable T{0, longest > 32, {}, 0, 0};
+    auto fill = [&](auto &pats) {
+        kmm_patterns((int32_t)idx.size(), codes.data(), off.data(), term, pats);
+        for (auto &P : pats) P.id = id_of ? id_of[idx[(size_t)P.id]] : idx[(size_t)P.id];
+        T.n = (int)pats.size();
+        put(T.bytes, pats.data(), pats.size());
+    };
+    if (T.two) { std::vector<KmmPat<2>> p; fill(p); } else { std::vector<KmmPat<1>> p; fill(p); }
+    return T;
+}
+
+// The table's rule.  max_gap < 0: b is a mismatch budget; max_gap >= 0: a penalty ceiling under the gapped rule — a table whose ceiling
+// admits a gap (5 + 3 g <= ceiling, g <= max_gap) goes through kmm_gap_kernel, the others through kmm_kernel with ceiling / 6
+// mismatches: the same sites.
+inline KmmTable kmm_budget(KmmTable T, int32_t b, int32_t max_gap) {
+    T.gaps = max_gap > 0 && b >= 8 ? std::min<int32_t>(max_gap, (b - 5) / 3) : 0;
+    T.budget = max_gap >= 0 && T.gaps == 0 ? b / 6 : b;
+    return T;
+}
+
+// one table per distinct budget[i], ascending (ids: the pattern's index), each under kmm_budget's rule
+inline std::vector<KmmTable> kmm_tables(int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *budget, int32_t max_gap,
+                                        int32_t term) {
+    std::vector<int32_t> budgets(budget, budget + n_pat);
+    std::sort(budgets.begin(), budgets.end());
+    budgets.erase(std::unique(budgets.begin(), budgets.end()), budgets.end());
+    std::vector<KmmTable> tables;
+    for (int32_t b : budgets) {
+        std::vector<int32_t> idx;
+        for (int32_t i = 0; i < n_pat; i++) if (budget[i] == b) idx.push_back(i);
+        tables.push_back(kmm_budget(kmm_table(idx, pat_codes, pat_off, nullptr, term), b, max_gap));
+    }
+    return tables;
+}
+
+inline size_t kmm_table_bytes(const std::vector<KmmTable> &tables) {      // room for the largest of them
+    size_t n = 1;
+    for (auto &T : tables) n = std::max(n, T.bytes.size());
+    return n;
+}
+
+// the text of a scan: the context's resident store, or (code == null) the bytes of the call
+struct KmmText {
+    const uint8_t *bytes;
+    const int64_t *roff;
+    const unsigned long long *code, *flag;
+    const int64_t *woff;
+};
+inline KmmText kmm_store(const mp_ctx *c) { return {c->sq_bytes, c->sq_roff, c->sq_code, c->sq_flag, c->sq_woff}; }
+
+// what a caller's launches may need beside kmm_kernel on the store (no kernel is compiled for a form its caller never takes)
+constexpr int kKmmBytes = 1;                     // the text may be the bytes of the call
+constexpr int kKmmGaps = 2;                      // a table may admit gaps
+
+template <int NW, int FORMS, class Sink>
+void kmm_launch_words(mp_ctx *c, const KmmText &X, const KmmBlocks &B, const KmmTable &T, const uint8_t *d_pats, int32_t term, const Sink &sink) {
+    const dim3 g((unsigned)B.size()), b(kBlock);
+    const KmmPat<NW> *pats = reinterpret_cast<const KmmPat<NW> *>(d_pats);
+    const int32_t *brow = B.d_row.p, *bseg = B.d_seg.p;
+    if constexpr ((FORMS & kKmmGaps) != 0) {
+        if (T.gaps > 0) {
+            hipLaunchKernelGGL((kmm_gap_kernel<NW, Sink>), g, b, 0, c->stream, X.roff, X.code, X.flag, X.woff, brow, bseg, pats, T.n, (int)T.budget,
+                               (int)T.gaps, (int)term, sink);
+            return;
+        }
+    }
+    if constexpr ((FORMS & kKmmBytes) != 0) {
+        if (!X.code) {
+            hipLaunchKernelGGL((kmm_kernel<NW, false, Sink>), g, b, 0, c->stream, X.bytes, X.roff, X.code, X.flag, X.woff, brow, bseg, pats, T.n,
+                               (int)T.budget, sink);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((kmm_kernel<NW, true, Sink>), g, b, 0, c->stream, X.bytes, X.roff, X.code, X.flag, X.woff, brow, bseg, pats, T.n, (int)T.budget, sink);
+}
+
+// One launch: table T (already at d_pats) over the workgroups B of text X into `sink`.  B.size() > 0.
+template <int FORMS, class Sink>
+hipError_t kmm_launch(mp_ctx *c, const KmmText &X, const KmmBlocks &B, const KmmTable &T, const uint8_t *d_pats, int32_t term, const Sink &sink) {
+    if (T.two) kmm_launch_words<2, FORMS>(c, X, B, T, d_pats, term, sink);
+    else kmm_launch_words<1, FORMS>(c, X, B, T, d_pats, term, sink);
+    return hipGetLastError();
 }
 
 }  // namespace

@@ -18,8 +18,6 @@
 #include "kmm.hpp"
 #include "../../include/mprime_offtarget.h"
 
-#include <tuple>
-
 using namespace mp;
 
 namespace {
@@ -241,95 +239,83 @@ __global__ __launch_bounds__(kBlock) void join_emit_kernel(JoinArgs A, const int
     }
 }
 
-inline unsigned grid(long long n, long long per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
-
 // exclusive scan of n int64 into out[0..n] (device arrays; `out` may not alias `in`)
 int scan_i64(mp_ctx *c, const long long *in, long long n, long long *out) {
     const long long n_part = (n + kScanTile - 1) / kScanTile;
-    long long *part = nullptr;
+    DevBuf<long long> part(c);
     int rc;
-    if ((rc = dev_alloc(c, &part, (size_t)n_part + 1))) return rc;
-    if (n_part) hipLaunchKernelGGL(scan_tiles_kernel, dim3(grid(n, kScanTile)), dim3(kBlock), 0, c->stream, in, n, part);
-    hipLaunchKernelGGL(scan_parts_kernel, dim3(1), dim3(kBlock), 0, c->stream, part, n_part, out + n);
-    if (n_part) hipLaunchKernelGGL(scan_apply_kernel, dim3(grid(n, kScanTile)), dim3(kBlock), 0, c->stream, in, n, (const long long *)part, out);
-    hipError_t e = hipGetLastError();
-    dev_free(c, &part, (size_t)n_part + 1);
+    if ((rc = part.alloc((size_t)n_part + 1))) return rc;
+    if (n_part) hipLaunchKernelGGL(scan_tiles_kernel, dim3(grid(n, kScanTile)), dim3(kBlock), 0, c->stream, in, n, part.p);
+    hipLaunchKernelGGL(scan_parts_kernel, dim3(1), dim3(kBlock), 0, c->stream, part.p, n_part, out + n);
+    if (n_part) hipLaunchKernelGGL(scan_apply_kernel, dim3(grid(n, kScanTile)), dim3(kBlock), 0, c->stream, in, n, (const long long *)part.p, out);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "scan: %s", hipGetErrorString(e));
     return MP_OK;
+}
+
+// the six-column products on the device go: another call's, or this call's once they were copied out
+void drop_products(mp_ctx *c) {
+    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
+    c->ot_n = 0;
 }
 
 // Everything after the sites: sites [0, n_fwd) forward, [n_fwd, n_sites) reverse (key n_bases + position key), rows keyed by row_key
 // (int32 per row: the sequence order is ascending (row_key, row)).  Products into c->ot_out (c->ot_n of them).
 int join_device(mp_ctx *c, const long long *d_key, const int32_t *d_primer, long long n_sites, const int64_t *d_roff, int n_rows,
                 long long n_bases, const int32_t *d_row_key, int32_t size_lo, int32_t size_hi) {
-    long long *f_lo = nullptr, *r_lo = nullptr, *cnt = nullptr, *off = nullptr, *rtot = nullptr, *rbase = nullptr;
-    unsigned long long *genes = nullptr;
-    int32_t *site_row = nullptr, *dead = nullptr;
+    DevBuf<long long> f_lo(c), r_lo(c), rtot(c), rbase(c), cnt(c), off(c);
+    DevBuf<int32_t> dead(c), site_row(c);
+    DevBuf<unsigned long long> genes(c);
     const size_t nr1 = (size_t)n_rows + 1;
+    int rc;
+    if ((rc = f_lo.alloc(nr1)) || (rc = r_lo.alloc(nr1)) || (rc = rtot.alloc(nr1)) || (rc = rbase.alloc(nr1)) || (rc = dead.alloc(nr1)) ||
+        (rc = genes.alloc(3))) return rc;
+    hipLaunchKernelGGL(site_rows_kernel, dim3(grid(n_rows + 1, kBlock)), dim3(kBlock), 0, c->stream, d_key, n_sites, d_roff, n_rows, n_bases, f_lo.p, r_lo.p);
+    HIPCK_WAIT(c, hipGetLastError());
     long long n_fwd = 0;
-    int rc = MP_OK;
-    hipError_t e = hipSuccess;
-    auto cleanup = [&]() {
-        dev_free(c, &f_lo, nr1); dev_free(c, &r_lo, nr1); dev_free(c, &rtot, nr1); dev_free(c, &rbase, nr1); dev_free(c, &dead, nr1);
-        dev_free(c, &genes, 3);
-    };
-    if ((rc = dev_alloc(c, &f_lo, nr1)) || (rc = dev_alloc(c, &r_lo, nr1)) || (rc = dev_alloc(c, &rtot, nr1)) || (rc = dev_alloc(c, &rbase, nr1)) ||
-        (rc = dev_alloc(c, &dead, nr1)) || (rc = dev_alloc(c, &genes, 3))) { cleanup(); return rc; }
-    hipLaunchKernelGGL(site_rows_kernel, dim3(grid(n_rows + 1, kBlock)), dim3(kBlock), 0, c->stream, d_key, n_sites, d_roff, n_rows, n_bases, f_lo, r_lo);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&n_fwd, f_lo + n_rows, sizeof n_fwd, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget sites: %s", hipGetErrorString(e)); }
+    HIPCK_WAIT(c, hipMemcpyAsync(&n_fwd, f_lo.p + n_rows, sizeof n_fwd, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
     c->ot_counts[1] = n_fwd;
     c->ot_counts[2] = n_sites - n_fwd;
-    JoinArgs A{d_key, d_primer, d_roff, n_rows, n_bases, n_fwd, f_lo, r_lo, size_lo, size_hi};
+    JoinArgs A{d_key, d_primer, d_roff, n_rows, n_bases, n_fwd, f_lo.p, r_lo.p, size_lo, size_hi};
     const size_t nf = (size_t)std::max<long long>(n_fwd, 1);
-    if ((rc = dev_alloc(c, &site_row, nf)) || (rc = dev_alloc(c, &cnt, nf)) || (rc = dev_alloc(c, &off, nf + 1))) {
-        dev_free(c, &site_row, nf); dev_free(c, &cnt, nf); dev_free(c, &off, nf + 1); cleanup(); return rc;
-    }
-    auto cleanup2 = [&]() { dev_free(c, &site_row, nf); dev_free(c, &cnt, nf); dev_free(c, &off, nf + 1); cleanup(); };
-    FillSeg segs[2] = {{dead, nr1 * 4, 0x7fffffffu}, {genes, 3 * sizeof(unsigned long long), 0u}};
-    if ((rc = fill_segments(c, segs, 2))) { cleanup2(); return rc; }
+    if ((rc = site_row.alloc(nf)) || (rc = cnt.alloc(nf)) || (rc = off.alloc(nf + 1))) return rc;
+    FillSeg segs[2] = {{dead.p, nr1 * 4, 0x7fffffffu}, {genes.p, 3 * sizeof(unsigned long long), 0u}};
+    if ((rc = fill_segments(c, segs, 2))) return rc;
     if (n_fwd) {
-        hipLaunchKernelGGL(join_count_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, site_row, cnt, dead);
-        hipLaunchKernelGGL(join_cut_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, (const int32_t *)site_row, (const int32_t *)dead, cnt);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(join_count_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, site_row.p, cnt.p, dead.p);
+        hipLaunchKernelGGL(join_cut_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, (const int32_t *)site_row.p, (const int32_t *)dead.p, cnt.p);
+        HIPCK_WAIT(c, hipGetLastError());
     }
-    if (e == hipSuccess && (rc = scan_i64(c, cnt, n_fwd, off))) { cleanup2(); return rc; }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(join_rows_kernel, dim3(grid(n_rows, kBlock)), dim3(kBlock), 0, c->stream, A, (const long long *)off, rtot, genes);
-        e = hipGetLastError();
-    }
+    if ((rc = scan_i64(c, cnt.p, n_fwd, off.p))) return rc;
+    hipLaunchKernelGGL(join_rows_kernel, dim3(grid(n_rows, kBlock)), dim3(kBlock), 0, c->stream, A, (const long long *)off.p, rtot.p, genes.p);
+    HIPCK_WAIT(c, hipGetLastError());
     // the sequence order: per-row totals and keys to the host (O(rows)), sorted there, the bases back
     std::vector<long long> h_tot((size_t)n_rows), h_base((size_t)n_rows, 0);
     std::vector<int32_t> h_key((size_t)n_rows);
-    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_tot.data(), rtot, sizeof(long long) * n_rows, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_key.data(), d_row_key, sizeof(int32_t) * n_rows, hipMemcpyDeviceToHost, c->stream);
     unsigned long long h_genes[3] = {0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(h_genes, genes, sizeof h_genes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup2(); return fail(c, MP_ERR_DEVICE, "offtarget join: %s", hipGetErrorString(e)); }
+    if (n_rows) {
+        HIPCK_WAIT(c, hipMemcpyAsync(h_tot.data(), rtot.p, sizeof(long long) * n_rows, hipMemcpyDeviceToHost, c->stream));
+        HIPCK_WAIT(c, hipMemcpyAsync(h_key.data(), d_row_key, sizeof(int32_t) * n_rows, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK_WAIT(c, hipMemcpyAsync(h_genes, genes.p, sizeof h_genes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < 3; i++) c->ot_counts[4 + i] = (int64_t)h_genes[i];
     std::vector<std::pair<int32_t, int32_t>> order;
     for (int r = 0; r < n_rows; r++) if (h_tot[(size_t)r]) order.push_back({h_key[(size_t)r], r});
     std::sort(order.begin(), order.end());
     long long total = 0;
     for (auto &kr : order) { h_base[(size_t)kr.second] = total; total += h_tot[(size_t)kr.second]; }
-    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
-    c->ot_n = 0;
-    if ((rc = dev_alloc(c, &c->ot_out, (size_t)std::max<long long>(total, 1) * 6))) { cleanup2(); return rc; }
+    drop_products(c);
+    if ((rc = dev_alloc(c, &c->ot_out, (size_t)std::max<long long>(total, 1) * 6))) return rc;
     c->ot_n = total;
     if (total) {
-        e = hipMemcpyAsync(rbase, h_base.data(), sizeof(long long) * n_rows, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(join_emit_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, (const int32_t *)site_row,
-                               (const long long *)off, (const long long *)rbase, c->ot_out);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);       // (h_base leaves scope)
+        HIPCK_WAIT(c, rbase.upload(h_base.data(), (size_t)n_rows));
+        hipLaunchKernelGGL(join_emit_kernel, dim3(grid(n_fwd, kBlock)), dim3(kBlock), 0, c->stream, A, (const int32_t *)site_row.p,
+                           (const long long *)off.p, (const long long *)rbase.p, c->ot_out);
+        HIPCK_WAIT(c, hipGetLastError());
+        HIPCK(c, hipStreamSynchronize(c->stream));          // (h_base leaves scope)
     }
-    cleanup2();
-    if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "offtarget emit: %s", hipGetErrorString(e));
     c->ot_counts[3] = total;
     return MP_OK;
 }
@@ -345,14 +331,72 @@ int copy_out(mp_ctx *c, int64_t cap, int32_t *out, int64_t *n_out) {
     return MP_OK;
 }
 
-template <class T> void put(std::vector<uint8_t> &k, const T *p, size_t n) {
-    const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
-    k.insert(k.end(), b, b + sizeof(T) * n);
-}
+// ---- the screen: a scan into a site map, then the map's sites in order ---------------------------------------------------------------
+// What both screens do between their arguments and their joins.  The map has `segments` segments of one entry per base of the store;
+// which of them a hit lands in is the sink's business.  The block list and the pattern tables live on the host as long as the object:
+// their copies are covered by the wait in reduce(), and by the destructor's when a call fails before it.
+struct Screen {
+    mp_ctx *c;
+    const long long n_bases, n_map, n_chunks;
+    KmmBlocks blocks;
+    std::vector<KmmTable> tables;
+    DevBuf<uint32_t> map;
+    DevBuf<uint8_t> pats;
+    DevBuf<unsigned long long> d_hits;
+    DevBuf<long long> ccnt, cbase, key;      // key / primer: the n_sites sites of the map, ascending in map order
+    DevBuf<int32_t> primer;
+    long long n_sites = 0;
+    unsigned long long hits = 0;             // hits of the scan, before the map folded them
+    bool in_flight = false;
 
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
+    Screen(mp_ctx *ctx, int segments)
+        : c(ctx), n_bases((long long)ctx->sq_total), n_map(segments * n_bases), n_chunks((n_map + kChunk - 1) / kChunk), blocks(ctx), map(ctx),
+          pats(ctx), d_hits(ctx), ccnt(ctx), cbase(ctx), key(ctx), primer(ctx) {}
+    ~Screen() { if (in_flight) (void)hipStreamSynchronize(c->stream); }
+
+    // one pattern table per budget (kmm_tables), the workgroups of the store, every buffer whose size the host knows
+    int open(int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *budget, int32_t max_gap, int32_t term) {
+        tables = kmm_tables(n_pat, pat_codes, pat_off, budget, max_gap, term);
+        int rc;
+        if ((rc = blocks.build(c->sq_roff_host.data(), c->sq_n)) || (rc = map.alloc((size_t)n_map)) || (rc = pats.alloc(kmm_table_bytes(tables))) ||
+            (rc = d_hits.alloc(1)) || (rc = ccnt.alloc((size_t)n_chunks)) || (rc = cbase.alloc((size_t)n_chunks + 1))) return rc;
+        return MP_OK;
+    }
+    int clear() {
+        in_flight = true;
+        HIPCK(c, map.zero());
+        HIPCK(c, d_hits.zero());
+        HIPCK(c, blocks.upload());
+        return MP_OK;
+    }
+    // one launch per table
+    template <int FORMS, class Sink> int scan(int32_t term, const Sink &sink) {
+        for (auto &T : tables) {
+            if (blocks.size() == 0) break;
+            // (from the second table on the copy overwrites pats: it waits for the launch before it on the stream)
+            HIPCK(c, pats.upload(T.bytes.data(), T.bytes.size()));
+            HIPCK(c, kmm_launch<FORMS>(c, kmm_store(c), blocks, T, pats.p, term, sink));
+        }
+        return MP_OK;
+    }
+    // the map's sites in order: key = map index, primer = d_read_id[read]
+    int reduce(const int32_t *d_read_id) {
+        hipLaunchKernelGGL(map_count_kernel, dim3(grid(n_map, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map.p, n_map, ccnt.p);
+        HIPCK(c, hipGetLastError());
+        int rc;
+        if ((rc = scan_i64(c, ccnt.p, n_chunks, cbase.p))) return rc;
+        HIPCK(c, hipMemcpyAsync(&n_sites, cbase.p + n_chunks, sizeof n_sites, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipMemcpyAsync(&hits, d_hits.p, sizeof hits, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));          // (the block list and the pattern tables may go now)
+        in_flight = false;
+        const size_t ns = (size_t)std::max<long long>(n_sites, 1);
+        if ((rc = key.alloc(ns)) || (rc = primer.alloc(ns))) return rc;
+        hipLaunchKernelGGL(map_write_kernel, dim3(grid(n_map, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map.p, n_map,
+                           (const long long *)cbase.p, d_read_id, key.p, primer.p);
+        HIPCK(c, hipGetLastError());
+        return MP_OK;
+    }
+};
 
 // The screen behind both entry points.  max_gap < 0: mp_offtarget_resident — max_mm[i] is read i's mismatch budget (kmm_kernel);
 // max_gap >= 0: mp_offtarget_gap_resident — max_mm[i] is read i's penalty ceiling, and a table whose ceiling admits a gap goes through
@@ -367,19 +411,13 @@ int offtarget_run(mp_ctx *c, const char *who, int32_t n_pat, const uint8_t *pat_
     const auto t0 = std::chrono::steady_clock::now();
     *n_out = 0;
     for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
-    for (int32_t i = 0; i < n_pat; i++) {
-        const int len = pat_off[i + 1] - pat_off[i];
-        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
-        for (int j = 0; j < len; j++) {
-            const uint8_t m = pat_codes[pat_off[i] + j];
-            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
-        }
-        if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative %s", i, max_gap < 0 ? "mismatch budget" : "penalty ceiling");
-    }
+    int rc;
+    if ((rc = kmm_check_patterns(c, n_pat, pat_codes, pat_off, [&](int32_t i) {
+            return max_mm[i] < 0 ? fail(c, MP_ERR_ARG, "pattern %d has a negative %s", i, max_gap < 0 ? "mismatch budget" : "penalty ceiling") : MP_OK;
+        }))) return rc;
     if (c->sq_n == 0 || n_pat == 0) {
         for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
-        dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
-        c->ot_n = 0;
+        drop_products(c);
         c->ot_key.clear();
         return MP_OK;
     }
@@ -392,149 +430,35 @@ int offtarget_run(mp_ctx *c, const char *who, int32_t n_pat, const uint8_t *pat_
     put(key, read_primer, (size_t)n_pat);
     put(key, max_mm, (size_t)n_pat);
     if (!c->ot_key.empty() && key == c->ot_key) {
-        int rc = copy_out(c, cap, out, n_out);
+        rc = copy_out(c, cap, out, n_out);
         c->ot_ms[3] = ms_since(t0);
         return rc;
     }
     c->ot_key.clear();
     for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
-    const long long n_bases = (long long)c->sq_total, n2 = 2 * n_bases;
     const int n_rows = c->sq_n;
-    // the workgroups of the scan: (row, segment) as in mp_kmm_scan
-    std::vector<int32_t> blk_row, blk_seg;
-    for (int32_t r = 0; r < n_rows; r++) {
-        const int64_t len = c->sq_roff_host[(size_t)r + 1] - c->sq_roff_host[(size_t)r];
-        for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
-    }
-    const size_t nb = std::max<size_t>(blk_row.size(), 1);
-    // one pattern table per mismatch budget / penalty ceiling (ids: the global read index)
-    std::vector<int32_t> budgets(max_mm, max_mm + n_pat);
-    std::sort(budgets.begin(), budgets.end());
-    budgets.erase(std::unique(budgets.begin(), budgets.end()), budgets.end());
-    struct Table { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; int32_t gaps; };
-    std::vector<Table> tables;
-    for (int32_t b : budgets) {
-        std::vector<uint8_t> codes;
-        std::vector<int32_t> off{0}, ids;
-        int longest = 0;
-        for (int32_t i = 0; i < n_pat; i++) {
-            if (max_mm[i] != b) continue;
-            codes.insert(codes.end(), pat_codes + pat_off[i], pat_codes + pat_off[i + 1]);
-            off.push_back((int32_t)codes.size());
-            ids.push_back(i);
-            longest = std::max(longest, pat_off[i + 1] - pat_off[i]);
-        }
-        // gap lengths this ceiling admits (5 + 3 g <= ceiling); none: kmm_kernel with ceiling / 6 mismatches
-        Table T{b, longest > 32, {}, 0, max_gap > 0 && b >= 8 ? std::min<int32_t>(max_gap, (b - 5) / 3) : 0};
-        if (max_gap >= 0 && T.gaps == 0) T.budget = b / 6;
-        auto fill = [&](auto &pats) {
-            kmm_patterns(off.size() - 1, codes.data(), off.data(), term, pats);
-            for (auto &P : pats) P.id = ids[(size_t)P.id];
-            T.n = (int)pats.size();
-            put(T.bytes, pats.data(), pats.size());
-        };
-        if (T.two) { std::vector<KmmPat<2>> p; fill(p); } else { std::vector<KmmPat<1>> p; fill(p); }
-        tables.push_back(std::move(T));
-    }
-    size_t pat_bytes = 1;
-    for (auto &T : tables) pat_bytes = std::max(pat_bytes, T.bytes.size());
-
-    uint32_t *map = nullptr;
-    int32_t *row_min = nullptr, *d_brow = nullptr, *d_bseg = nullptr, *d_rp = nullptr, *primer = nullptr;
-    uint8_t *d_pats = nullptr;
-    unsigned long long *d_hits = nullptr;
-    long long *ccnt = nullptr, *cbase = nullptr, *skey = nullptr;
-    const long long n_chunks = (n2 + kChunk - 1) / kChunk;
-    long long n_sites = 0;
-    size_t ns = 1;
-    auto cleanup = [&]() {
-        dev_free(c, &map, (size_t)n2); dev_free(c, &row_min, (size_t)n_rows); dev_free(c, &d_brow, nb); dev_free(c, &d_bseg, nb);
-        dev_free(c, &d_rp, (size_t)n_pat); dev_free(c, &d_pats, pat_bytes); dev_free(c, &d_hits, 1); dev_free(c, &ccnt, (size_t)n_chunks);
-        dev_free(c, &cbase, (size_t)n_chunks + 1); dev_free(c, &skey, ns); dev_free(c, &primer, ns);
-    };
-    int rc;
-    if ((rc = dev_alloc(c, &map, (size_t)n2)) || (rc = dev_alloc(c, &row_min, (size_t)n_rows)) || (rc = dev_alloc(c, &d_brow, nb)) ||
-        (rc = dev_alloc(c, &d_bseg, nb)) || (rc = dev_alloc(c, &d_rp, (size_t)n_pat)) || (rc = dev_alloc(c, &d_pats, pat_bytes)) ||
-        (rc = dev_alloc(c, &d_hits, 1)) || (rc = dev_alloc(c, &ccnt, (size_t)n_chunks)) || (rc = dev_alloc(c, &cbase, (size_t)n_chunks + 1))) {
-        cleanup(); return rc;
-    }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
-    auto destroy_events = [&]() { for (auto &x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(map, 0, sizeof(uint32_t) * (size_t)n2, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess && !blk_row.empty()) {
-        e = hipMemcpyAsync(d_brow, blk_row.data(), sizeof(int32_t) * blk_row.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_bseg, blk_seg.data(), sizeof(int32_t) * blk_seg.size(), hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rp, read_primer, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
-    FillSeg seg{row_min, sizeof(int32_t) * (size_t)n_rows, 0x7fffffffu};
-    if ((rc = fill_segments(c, &seg, 1))) { destroy_events(); cleanup(); return rc; }
-    OtSites sink{map, c->sq_roff, n_bases, row_min, d_hits};
-    for (auto &T : tables) {
-        if (blk_row.empty()) break;
-        e = hipMemcpyAsync(d_pats, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) break;
-        if (T.gaps > 0 && T.two)
-            hipLaunchKernelGGL((kmm_gap_kernel<2, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const int64_t *)c->sq_roff,
-                               (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag, (const int64_t *)c->sq_woff,
-                               (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats), T.n, (int)T.budget,
-                               (int)T.gaps, (int)term, sink);
-        else if (T.gaps > 0)
-            hipLaunchKernelGGL((kmm_gap_kernel<1, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const int64_t *)c->sq_roff,
-                               (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag, (const int64_t *)c->sq_woff,
-                               (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<1> *>(d_pats), T.n, (int)T.budget,
-                               (int)T.gaps, (int)term, sink);
-        else if (T.two)
-            hipLaunchKernelGGL((kmm_kernel<2, true, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
-                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
-                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats),
-                               T.n, (int)T.budget, sink);
-        else
-            hipLaunchKernelGGL((kmm_kernel<1, true, OtSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
-                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
-                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<1> *>(d_pats),
-                               T.n, (int)T.budget, sink);
-        e = hipGetLastError();
-        // the next table overwrites d_pats: the copy waits for this launch on the stream, the host array stays alive until the end
-        if (e != hipSuccess) break;
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-    // reduce: the map's sites in order
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(map_count_kernel, dim3(grid(n2, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n2, ccnt);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget scan: %s", hipGetErrorString(e)); }
-    if ((rc = scan_i64(c, ccnt, n_chunks, cbase))) { (void)hipStreamSynchronize(c->stream); destroy_events(); cleanup(); return rc; }
-    unsigned long long h_hits = 0;
-    e = hipMemcpyAsync(&n_sites, cbase + n_chunks, sizeof n_sites, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_hits, d_hits, sizeof h_hits, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the pattern tables may go now)
-    if (e != hipSuccess) { destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget reduce: %s", hipGetErrorString(e)); }
-    ns = (size_t)std::max<long long>(n_sites, 1);
-    if ((rc = dev_alloc(c, &skey, ns)) || (rc = dev_alloc(c, &primer, ns))) { destroy_events(); cleanup(); return rc; }
-    hipLaunchKernelGGL(map_write_kernel, dim3(grid(n2, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n2, (const long long *)cbase,
-                       (const int32_t *)d_rp, skey, primer);
-    e = hipGetLastError();
-    dev_free(c, &map, (size_t)n2);                                  // (released blocks are ordered on the stream: pool_give records an event)
-    if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); destroy_events(); cleanup(); return fail(c, MP_ERR_DEVICE, "offtarget reduce: %s", hipGetErrorString(e)); }
-    rc = join_device(c, skey, primer, n_sites, c->sq_roff, n_rows, n_bases, row_min, size_lo, size_hi);
-    if (rc == MP_OK) {
-        e = hipEventRecord(ev[3], c->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
-        float ms = 0;
-        for (int i = 0; i < 3 && e == hipSuccess; i++) { e = hipEventElapsedTime(&ms, ev[i], ev[i + 1]); c->ot_ms[i] = ms; }
-        if (e != hipSuccess) rc = fail(c, MP_ERR_DEVICE, "offtarget timing: %s", hipGetErrorString(e));
-    }
-    destroy_events();
-    cleanup();
-    if (rc != MP_OK) return rc;
-    c->ot_counts[0] = (int64_t)h_hits;
+    Screen X(c, 2);
+    DevBuf<int32_t> row_min(c), d_rp(c);
+    if ((rc = X.open(n_pat, pat_codes, pat_off, max_mm, max_gap, term)) || (rc = row_min.alloc((size_t)n_rows)) || (rc = d_rp.alloc((size_t)n_pat))) return rc;
+    StageClock scan, reduce, join;           // the stage times are device times: one stage ends where the next begins
+    scan.begin(c);
+    if ((rc = X.clear())) return rc;
+    HIPCK(c, d_rp.upload(read_primer, (size_t)n_pat));
+    FillSeg seg{row_min.p, sizeof(int32_t) * (size_t)n_rows, 0x7fffffffu};
+    if ((rc = fill_segments(c, &seg, 1))) return rc;
+    if ((rc = X.scan<kKmmGaps>(term, OtSites{X.map.p, c->sq_roff, X.n_bases, row_min.p, X.d_hits.p}))) return rc;
+    scan.end(c);
+    reduce.begin(c);
+    if ((rc = X.reduce(d_rp.p))) return rc;
+    X.map.release();            // the largest block of the call: the join takes it back from the pool (a released block is ordered on the stream)
+    reduce.end(c);
+    join.begin(c);
+    if ((rc = join_device(c, X.key.p, X.primer.p, X.n_sites, c->sq_roff, n_rows, X.n_bases, row_min.p, size_lo, size_hi))) return rc;
+    join.end(c);
+    join.read(c->ot_ms + 2);
+    scan.read(c->ot_ms);
+    reduce.read(c->ot_ms + 1);
+    c->ot_counts[0] = (int64_t)X.hits;
     c->ot_key = std::move(key);
     rc = copy_out(c, cap, out, n_out);
     c->ot_ms[3] = ms_since(t0);
@@ -600,8 +524,7 @@ int join_one_class(mp_ctx *c, const long long *d_key, const int32_t *d_primer, l
         out7.push_back(cls);
     }
     for (int i = 1; i < kOtCounts; i++) acc[i] += c->ot_counts[i];
-    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);          // the six-column products belong to no store
-    c->ot_n = 0;
+    drop_products(c);                                       // the six-column products belong to no store
     return MP_OK;
 }
 
@@ -613,59 +536,84 @@ int copy_out7(const std::vector<int32_t> &all, int64_t cap, int32_t *out, int64_
     return MP_OK;
 }
 
+// ---- explicit sites (mp_amplicon_join, mp_amplicon_join_classes) ---------------------------------------------------------------------
+// Sites of w int32 each: w - 3 leading columns of 0 | 1 (strand; class and strand), then row, position and an id, strictly ascending in
+// all but the id.  Their rows as a join sees them: position key row << 32 | position, sequences in ascending row order.
+struct SiteRows {
+    int n_rows = 0;
+    long long n_bases = 0;
+    std::vector<int32_t> row_key;            // (the host tables live with the object: upload() is covered by the caller's next wait)
+    std::vector<int64_t> roff;
+    DevBuf<int32_t> d_rkey;
+    DevBuf<int64_t> d_roff;
+    explicit SiteRows(mp_ctx *c) : d_rkey(c), d_roff(c) {}
+    // `shape` and `order` describe a site and its ordering columns in the messages
+    int open(const char *who, int64_t n_sites, const int32_t *sites, int w, const char *shape, const char *order) {
+        mp_ctx *c = d_rkey.c;
+        int32_t max_row = 0;
+        for (int64_t i = 0; i < n_sites; i++) {
+            const int32_t *s = sites + w * i, *row = s + w - 3;
+            bool ok = row[0] >= 0 && row[1] >= 0;
+            for (int k = 0; k < w - 3; k++) ok = ok && (s[k] == 0 || s[k] == 1);
+            if (!ok) return fail(c, MP_ERR_ARG, "%s: site %lld is not {%s}", who, (long long)i, shape);
+            if (row[0] >= (1 << 29)) return fail(c, MP_ERR_ARG, "%s: row %d of site %lld: at most 2^29 rows", who, row[0], (long long)i);
+            if (i && !std::lexicographical_compare(s - w, s - 1, s, s + w - 1))
+                return fail(c, MP_ERR_ARG, "%s: sites must ascend strictly in (%s) (site %lld)", who, order, (long long)i);
+            max_row = std::max(max_row, row[0]);
+        }
+        n_rows = max_row + 1;
+        n_bases = (long long)n_rows << 32;
+        row_key.resize((size_t)n_rows);
+        roff.resize((size_t)n_rows + 1);
+        for (int r = 0; r <= n_rows; r++) roff[(size_t)r] = (int64_t)r << 32;
+        for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;
+        int rc;
+        if ((rc = d_rkey.alloc(row_key.size())) || (rc = d_roff.alloc(roff.size()))) return rc;
+        return MP_OK;
+    }
+    hipError_t upload() {
+        const hipError_t e = d_rkey.upload(row_key.data(), row_key.size());
+        return e == hipSuccess ? d_roff.upload(roff.data(), roff.size()) : e;
+    }
+};
+
+// what every entry of explicit sites starts with: they replace whatever the resident screen kept
+void begin_explicit(mp_ctx *c, int64_t *n_out) {
+    *n_out = 0;
+    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
+    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
+    drop_products(c);
+    c->ot_key.clear();
+}
+
 }  // namespace
 
 extern "C" {
 
 int mp_amplicon_join_classes(mp_ctx *c, int64_t n_sites, const int32_t *sites, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out,
                              int64_t *n_out) {
+    const char *who = "mp_amplicon_join_classes";
     if (!c) return MP_ERR_ARG;
-    if (n_sites < 0 || !n_out || cap < 0 || (cap && !out) || (n_sites && !sites)) return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: bad arguments");
+    if (n_sites < 0 || !n_out || cap < 0 || (cap && !out) || (n_sites && !sites)) return fail(c, MP_ERR_ARG, "%s: bad arguments", who);
     HIPCK(c, hipSetDevice(c->dev));
     const auto t0 = std::chrono::steady_clock::now();
-    *n_out = 0;
-    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
-    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
-    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);           // explicit sites replace whatever the resident screen kept
-    c->ot_n = 0;
-    c->ot_key.clear();
+    begin_explicit(c, n_out);
     if (n_sites == 0) return MP_OK;
-    int32_t max_row = 0;
+    SiteRows R(c);
+    int rc;
+    if ((rc = R.open(who, n_sites, sites, 5, "0|1, 0|1, row >= 0, pos >= 0, read", "class, strand, row, position"))) return rc;
     std::vector<long long> seg_key[4];
     std::vector<int32_t> seg_read[4];
     for (int64_t i = 0; i < n_sites; i++) {
         const int32_t *s = sites + 5 * i;
-        if ((s[0] != 0 && s[0] != 1) || (s[1] != 0 && s[1] != 1) || s[2] < 0 || s[3] < 0)
-            return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: site %lld is not {0|1, 0|1, row >= 0, pos >= 0, read}", (long long)i);
-        if (s[2] >= (1 << 29)) return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: row %d of site %lld: at most 2^29 rows", s[2], (long long)i);
-        if (i) {
-            const int32_t *p = s - 5;
-            if (std::make_tuple(p[0], p[1], p[2], p[3]) >= std::make_tuple(s[0], s[1], s[2], s[3]))
-                return fail(c, MP_ERR_ARG, "mp_amplicon_join_classes: sites must ascend strictly in (class, strand, row, position) (site %lld)", (long long)i);
-        }
-        max_row = std::max(max_row, s[2]);
         seg_key[2 * s[0] + s[1]].push_back(((long long)s[2] << 32) + s[3]);
         seg_read[2 * s[0] + s[1]].push_back(s[4]);
     }
-    const int n_rows = max_row + 1;
-    const long long n_bases = (long long)n_rows << 32;
-    std::vector<int32_t> row_key((size_t)n_rows);
-    std::vector<int64_t> roff((size_t)n_rows + 1);
-    for (int r = 0; r <= n_rows; r++) roff[(size_t)r] = (int64_t)r << 32;
-    for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;
-    long long *d_key = nullptr;
-    int32_t *d_primer = nullptr, *d_rkey = nullptr;
-    int64_t *d_roff = nullptr;
-    const size_t ns = (size_t)n_sites, nr = (size_t)n_rows;
-    auto cleanup = [&]() { dev_free(c, &d_key, ns); dev_free(c, &d_primer, ns); dev_free(c, &d_rkey, nr); dev_free(c, &d_roff, nr + 1); };
-    int rc;
-    if ((rc = dev_alloc(c, &d_key, ns)) || (rc = dev_alloc(c, &d_primer, ns)) || (rc = dev_alloc(c, &d_rkey, nr)) || (rc = dev_alloc(c, &d_roff, nr + 1))) {
-        cleanup(); return rc;
-    }
-    hipError_t e = hipMemcpyAsync(d_rkey, row_key.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "mp_amplicon_join_classes: %s", hipGetErrorString(e)); }
+    DevBuf<long long> d_key(c);
+    DevBuf<int32_t> d_primer(c);
+    if ((rc = d_key.alloc((size_t)n_sites)) || (rc = d_primer.alloc((size_t)n_sites))) return rc;
+    HIPCK_WAIT(c, R.upload());
+    HIPCK(c, hipStreamSynchronize(c->stream));
     std::vector<int32_t> all;
     int64_t acc[kOtCounts] = {0, 0, 0, 0, 0, 0, 0};
     for (int k = 0; k < kJoinClasses && rc == MP_OK; k++) {
@@ -673,16 +621,14 @@ int mp_amplicon_join_classes(mp_ctx *c, int64_t n_sites, const int32_t *sites, i
         if (fk.empty() || rk.empty()) continue;
         std::vector<long long> key(fk);
         std::vector<int32_t> primer(seg_read[kJoinFwd[k]]);
-        for (long long v : rk) key.push_back(n_bases + v);
+        for (long long v : rk) key.push_back(R.n_bases + v);
         primer.insert(primer.end(), seg_read[kJoinRev[k]].begin(), seg_read[kJoinRev[k]].end());
-        e = hipMemcpyAsync(d_key, key.data(), sizeof(long long) * key.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_primer, primer.data(), sizeof(int32_t) * primer.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = fail(c, MP_ERR_DEVICE, "mp_amplicon_join_classes: %s", hipGetErrorString(e)); break; }
-        rc = join_one_class(c, d_key, d_primer, (long long)key.size(), d_roff, n_rows, n_bases, d_rkey, size_lo, size_hi, k, all, acc);
+        HIPCK_WAIT(c, d_key.upload(key.data(), key.size()));
+        HIPCK_WAIT(c, d_primer.upload(primer.data(), primer.size()));
+        HIPCK(c, hipStreamSynchronize(c->stream));          // (key and primer leave scope)
+        rc = join_one_class(c, d_key.p, d_primer.p, (long long)key.size(), R.d_roff.p, R.n_rows, R.n_bases, R.d_rkey.p, size_lo, size_hi, k, all, acc);
     }
     (void)hipStreamSynchronize(c->stream);
-    cleanup();
     if (rc != MP_OK) return rc;
     for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = acc[i];
     rc = copy_out7(all, cap, out, n_out);
@@ -701,19 +647,14 @@ int mp_offtarget_classes(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, con
     const auto t0 = std::chrono::steady_clock::now();
     *n_out = 0;
     for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
-    for (int32_t i = 0; i < n_pat; i++) {
-        const int len = pat_off[i + 1] - pat_off[i];
-        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
-        for (int j = 0; j < len; j++) {
-            const uint8_t m = pat_codes[pat_off[i] + j];
-            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
-        }
-        if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative mismatch budget", i);
-        if (read_class[i] != 0 && read_class[i] != 1) return fail(c, MP_ERR_ARG, "pattern %d has class %d (0 core, 1 new)", i, read_class[i]);
-    }
+    int rc;
+    if ((rc = kmm_check_patterns(c, n_pat, pat_codes, pat_off, [&](int32_t i) {
+            if (max_mm[i] < 0) return fail(c, MP_ERR_ARG, "pattern %d has a negative mismatch budget", i);
+            if (read_class[i] != 0 && read_class[i] != 1) return fail(c, MP_ERR_ARG, "pattern %d has class %d (0 core, 1 new)", i, read_class[i]);
+            return (int)MP_OK;
+        }))) return rc;
     // the six-column products of the plain screen do not survive this call (join_device reuses their buffer)
-    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
-    c->ot_n = 0;
+    drop_products(c);
     c->ot_key.clear();
     if (c->sq_n == 0 || n_pat == 0) {
         for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
@@ -730,128 +671,38 @@ int mp_offtarget_classes(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, con
     put(key, read_class, (size_t)n_pat);
     put(key, max_mm, (size_t)n_pat);
     if (!c->otc_key.empty() && key == c->otc_key) {         // a repeat of the last call: nothing is scanned again
-        int rc = copy_out7(c->otc_out, cap, out, n_out);
+        rc = copy_out7(c->otc_out, cap, out, n_out);
         c->ot_ms[3] = ms_since(t0);
         return rc;
     }
     c->otc_key.clear();
     c->otc_out.clear();
     for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
-    const long long n_bases = (long long)c->sq_total, n4 = 4 * n_bases;
     const int n_rows = c->sq_n;
-    std::vector<int32_t> blk_row, blk_seg;
-    for (int32_t r = 0; r < n_rows; r++) {
-        const int64_t len = c->sq_roff_host[(size_t)r + 1] - c->sq_roff_host[(size_t)r];
-        for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
-    }
-    const size_t nb = std::max<size_t>(blk_row.size(), 1);
-    std::vector<int32_t> budgets(max_mm, max_mm + n_pat);
-    std::sort(budgets.begin(), budgets.end());
-    budgets.erase(std::unique(budgets.begin(), budgets.end()), budgets.end());
-    struct Table { int32_t budget; bool two; std::vector<uint8_t> bytes; int n; };
-    std::vector<Table> tables;
-    for (int32_t b : budgets) {
-        std::vector<uint8_t> codes;
-        std::vector<int32_t> off{0}, ids;
-        int longest = 0;
-        for (int32_t i = 0; i < n_pat; i++) {
-            if (max_mm[i] != b) continue;
-            codes.insert(codes.end(), pat_codes + pat_off[i], pat_codes + pat_off[i + 1]);
-            off.push_back((int32_t)codes.size());
-            ids.push_back(i);
-            longest = std::max(longest, pat_off[i + 1] - pat_off[i]);
-        }
-        Table T{b, longest > 32, {}, 0};
-        auto fill = [&](auto &pats) {
-            kmm_patterns(off.size() - 1, codes.data(), off.data(), term, pats);
-            for (auto &P : pats) P.id = ids[(size_t)P.id];
-            T.n = (int)pats.size();
-            put(T.bytes, pats.data(), pats.size());
-        };
-        if (T.two) { std::vector<KmmPat<2>> p; fill(p); } else { std::vector<KmmPat<1>> p; fill(p); }
-        tables.push_back(std::move(T));
-    }
-    size_t pat_bytes = 1;
-    for (auto &T : tables) pat_bytes = std::max(pat_bytes, T.bytes.size());
-
-    uint32_t *map = nullptr;
-    int32_t *d_brow = nullptr, *d_bseg = nullptr, *d_rid = nullptr, *d_rcls = nullptr, *primer = nullptr, *d_rkey = nullptr, *jprimer = nullptr;
-    uint8_t *d_pats = nullptr;
-    unsigned long long *d_hits = nullptr;
-    long long *ccnt = nullptr, *cbase = nullptr, *skey = nullptr, *d_bound = nullptr, *jkey = nullptr;
-    const long long n_chunks = (n4 + kChunk - 1) / kChunk;
-    long long n_sites = 0;
-    size_t ns = 1;
-    auto cleanup = [&]() {
-        dev_free(c, &map, (size_t)n4); dev_free(c, &d_brow, nb); dev_free(c, &d_bseg, nb); dev_free(c, &d_rid, (size_t)n_pat);
-        dev_free(c, &d_rcls, (size_t)n_pat); dev_free(c, &d_pats, pat_bytes); dev_free(c, &d_hits, 1); dev_free(c, &ccnt, (size_t)n_chunks);
-        dev_free(c, &cbase, (size_t)n_chunks + 1); dev_free(c, &skey, ns); dev_free(c, &primer, ns); dev_free(c, &d_rkey, (size_t)n_rows);
-        dev_free(c, &d_bound, 5); dev_free(c, &jkey, ns); dev_free(c, &jprimer, ns);
-    };
-    int rc;
-    if ((rc = dev_alloc(c, &map, (size_t)n4)) || (rc = dev_alloc(c, &d_brow, nb)) || (rc = dev_alloc(c, &d_bseg, nb)) ||
-        (rc = dev_alloc(c, &d_rid, (size_t)n_pat)) || (rc = dev_alloc(c, &d_rcls, (size_t)n_pat)) || (rc = dev_alloc(c, &d_pats, pat_bytes)) ||
-        (rc = dev_alloc(c, &d_hits, 1)) || (rc = dev_alloc(c, &ccnt, (size_t)n_chunks)) || (rc = dev_alloc(c, &cbase, (size_t)n_chunks + 1)) ||
-        (rc = dev_alloc(c, &d_rkey, (size_t)n_rows)) || (rc = dev_alloc(c, &d_bound, 5))) {
-        cleanup(); return rc;
-    }
     std::vector<int32_t> row_key((size_t)n_rows);
     for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;           // sequences in ascending store order
-    hipError_t e = hipMemsetAsync(map, 0, sizeof(uint32_t) * (size_t)n4, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess && !blk_row.empty()) {
-        e = hipMemcpyAsync(d_brow, blk_row.data(), sizeof(int32_t) * blk_row.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_bseg, blk_seg.data(), sizeof(int32_t) * blk_seg.size(), hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rid, read_id, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rcls, read_class, sizeof(int32_t) * n_pat, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rkey, row_key.data(), sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
+    Screen X(c, 4);
+    DevBuf<int32_t> d_rid(c), d_rcls(c), d_rkey(c), jprimer(c);
+    DevBuf<long long> d_bound(c), jkey(c);
+    if ((rc = X.open(n_pat, pat_codes, pat_off, max_mm, -1, term)) || (rc = d_rid.alloc((size_t)n_pat)) || (rc = d_rcls.alloc((size_t)n_pat)) ||
+        (rc = d_rkey.alloc((size_t)n_rows)) || (rc = d_bound.alloc(5))) return rc;
+    if ((rc = X.clear())) return rc;
+    HIPCK(c, d_rid.upload(read_id, (size_t)n_pat));
+    HIPCK(c, d_rcls.upload(read_class, (size_t)n_pat));
+    HIPCK(c, d_rkey.upload(row_key.data(), row_key.size()));
+    HIPCK(c, hipStreamSynchronize(c->stream));              // (the stage times of this screen are host times: each stage ends in a wait)
     const auto t_scan = std::chrono::steady_clock::now();
-    OtClassSites sink{map, c->sq_roff, n_bases, d_rcls, d_hits};
-    for (auto &T : tables) {
-        if (blk_row.empty()) break;
-        e = hipMemcpyAsync(d_pats, T.bytes.data(), T.bytes.size(), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) break;
-        if (T.two)
-            hipLaunchKernelGGL((kmm_kernel<2, true, OtClassSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
-                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
-                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<2> *>(d_pats),
-                               T.n, (int)T.budget, sink);
-        else
-            hipLaunchKernelGGL((kmm_kernel<1, true, OtClassSites>), dim3((unsigned)blk_row.size()), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
-                               (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
-                               (const int64_t *)c->sq_woff, (const int32_t *)d_brow, (const int32_t *)d_bseg, reinterpret_cast<const KmmPat<1> *>(d_pats),
-                               T.n, (int)T.budget, sink);
-        e = hipGetLastError();
-        if (e != hipSuccess) break;
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);          // (stage times on the host clock; the pattern tables may go now)
-    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s scan: %s", who, hipGetErrorString(e)); }
+    if ((rc = X.scan<0>(term, OtClassSites{X.map.p, c->sq_roff, X.n_bases, d_rcls.p, X.d_hits.p}))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
     c->ot_ms[0] = ms_since(t_scan);
     const auto t_red = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(map_count_kernel, dim3(grid(n4, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n4, ccnt);
-    e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); cleanup(); return fail(c, MP_ERR_DEVICE, "%s reduce: %s", who, hipGetErrorString(e)); }
-    if ((rc = scan_i64(c, ccnt, n_chunks, cbase))) { (void)hipStreamSynchronize(c->stream); cleanup(); return rc; }
-    unsigned long long h_hits = 0;
-    e = hipMemcpyAsync(&n_sites, cbase + n_chunks, sizeof n_sites, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_hits, d_hits, sizeof h_hits, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s reduce: %s", who, hipGetErrorString(e)); }
-    ns = (size_t)std::max<long long>(n_sites, 1);
-    if ((rc = dev_alloc(c, &skey, ns)) || (rc = dev_alloc(c, &primer, ns)) || (rc = dev_alloc(c, &jkey, ns)) || (rc = dev_alloc(c, &jprimer, ns))) {
-        cleanup(); return rc;
-    }
+    if ((rc = X.reduce(d_rid.p))) return rc;
+    if ((rc = jkey.alloc(X.key.n)) || (rc = jprimer.alloc(X.key.n))) return rc;
     long long bound[5] = {0, 0, 0, 0, 0};
-    hipLaunchKernelGGL(map_write_kernel, dim3(grid(n4, kChunk)), dim3(kBlock), 0, c->stream, (const uint32_t *)map, n4, (const long long *)cbase,
-                       (const int32_t *)d_rid, skey, primer);
-    hipLaunchKernelGGL(segment_bounds_kernel, dim3(1), dim3(64), 0, c->stream, (const long long *)skey, n_sites, n_bases, d_bound);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(bound, d_bound, sizeof bound, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, MP_ERR_DEVICE, "%s reduce: %s", who, hipGetErrorString(e)); }
+    hipLaunchKernelGGL(segment_bounds_kernel, dim3(1), dim3(64), 0, c->stream, (const long long *)X.key.p, X.n_sites, X.n_bases, d_bound.p);
+    HIPCK_WAIT(c, hipGetLastError());
+    HIPCK_WAIT(c, hipMemcpyAsync(bound, d_bound.p, sizeof bound, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
     c->ot_ms[1] = ms_since(t_red);
     const auto t_join = std::chrono::steady_clock::now();
     std::vector<int32_t> all;
@@ -860,17 +711,16 @@ int mp_offtarget_classes(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, con
         const int fs = kJoinFwd[k], rs = kJoinRev[k];
         const long long n_f = bound[fs + 1] - bound[fs], n_r = bound[rs + 1] - bound[rs];
         if (n_f == 0 || n_r == 0) continue;
-        hipLaunchKernelGGL(join_pick_kernel, dim3(grid(n_f + n_r, kBlock)), dim3(kBlock), 0, c->stream, (const long long *)skey, (const int32_t *)primer,
-                           bound[fs], n_f, (long long)fs * n_bases, bound[rs], n_r, (long long)rs * n_bases, n_bases, jkey, jprimer);
-        e = hipGetLastError();
-        if (e != hipSuccess) { rc = fail(c, MP_ERR_DEVICE, "%s join: %s", who, hipGetErrorString(e)); break; }
-        rc = join_one_class(c, jkey, jprimer, n_f + n_r, c->sq_roff, n_rows, n_bases, d_rkey, size_lo, size_hi, k, all, acc);
+        hipLaunchKernelGGL(join_pick_kernel, dim3(grid(n_f + n_r, kBlock)), dim3(kBlock), 0, c->stream, (const long long *)X.key.p,
+                           (const int32_t *)X.primer.p, bound[fs], n_f, (long long)fs * X.n_bases, bound[rs], n_r, (long long)rs * X.n_bases, X.n_bases,
+                           jkey.p, jprimer.p);
+        HIPCK_WAIT(c, hipGetLastError());
+        rc = join_one_class(c, jkey.p, jprimer.p, n_f + n_r, c->sq_roff, n_rows, X.n_bases, d_rkey.p, size_lo, size_hi, k, all, acc);
     }
     (void)hipStreamSynchronize(c->stream);
-    cleanup();
     if (rc != MP_OK) return rc;
     c->ot_ms[2] = ms_since(t_join);
-    acc[0] = (int64_t)h_hits;
+    acc[0] = (int64_t)X.hits;
     for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = acc[i];
     c->otc_out = std::move(all);
     c->otc_key = std::move(key);
@@ -892,76 +742,38 @@ int mp_offtarget_gap_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes
 }
 
 int mp_amplicon_join(mp_ctx *c, int64_t n_sites, const int32_t *sites, int32_t size_lo, int32_t size_hi, int64_t cap, int32_t *out, int64_t *n_out) {
+    const char *who = "mp_amplicon_join";
     if (!c) return MP_ERR_ARG;
-    if (n_sites < 0 || !n_out || cap < 0 || (cap && !out) || (n_sites && !sites)) return fail(c, MP_ERR_ARG, "mp_amplicon_join: bad arguments");
+    if (n_sites < 0 || !n_out || cap < 0 || (cap && !out) || (n_sites && !sites)) return fail(c, MP_ERR_ARG, "%s: bad arguments", who);
     HIPCK(c, hipSetDevice(c->dev));
     const auto t0 = std::chrono::steady_clock::now();
-    *n_out = 0;
-    for (int i = 0; i < 4; i++) c->ot_ms[i] = 0;
-    for (int i = 0; i < kOtCounts; i++) c->ot_counts[i] = 0;
-    // explicit sites replace whatever the resident screen kept
-    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
-    c->ot_n = 0;
-    c->ot_key.clear();
+    begin_explicit(c, n_out);
     if (n_sites == 0) return MP_OK;
-    int32_t max_row = 0;
-    for (int64_t i = 0; i < n_sites; i++) {
-        const int32_t *s = sites + 4 * i;
-        if ((s[0] != 0 && s[0] != 1) || s[1] < 0 || s[2] < 0) return fail(c, MP_ERR_ARG, "mp_amplicon_join: site %lld is not {0|1, row >= 0, pos >= 0, id}", (long long)i);
-        if (s[1] >= (1 << 29)) return fail(c, MP_ERR_ARG, "mp_amplicon_join: row %d of site %lld: at most 2^29 rows", s[1], (long long)i);
-        if (i) {
-            const int32_t *p = s - 4;
-            if (std::make_tuple(p[0], p[1], p[2]) >= std::make_tuple(s[0], s[1], s[2]))
-                return fail(c, MP_ERR_ARG, "mp_amplicon_join: sites must ascend strictly in (strand, row, position) (site %lld)", (long long)i);
-        }
-        max_row = std::max(max_row, s[1]);
-    }
-    const int n_rows = max_row + 1;
-    const long long n_bases = (long long)n_rows << 32;
+    SiteRows R(c);
+    int rc;
+    if ((rc = R.open(who, n_sites, sites, 4, "0|1, row >= 0, pos >= 0, id", "strand, row, position"))) return rc;
     std::vector<long long> key((size_t)n_sites);
-    std::vector<int32_t> primer((size_t)n_sites), row_key((size_t)n_rows);
-    std::vector<int64_t> roff((size_t)n_rows + 1);
+    std::vector<int32_t> primer((size_t)n_sites);
     for (int64_t i = 0; i < n_sites; i++) {
         const int32_t *s = sites + 4 * i;
-        key[(size_t)i] = (s[0] ? n_bases : 0) + ((long long)s[1] << 32) + s[2];
+        key[(size_t)i] = (s[0] ? R.n_bases : 0) + ((long long)s[1] << 32) + s[2];
         primer[(size_t)i] = s[3];
     }
-    for (int r = 0; r <= n_rows; r++) roff[(size_t)r] = (int64_t)r << 32;
-    for (int r = 0; r < n_rows; r++) row_key[(size_t)r] = r;
-    long long *d_key = nullptr;
-    int32_t *d_primer = nullptr, *d_rkey = nullptr;
-    int64_t *d_roff = nullptr;
-    const size_t ns = (size_t)n_sites, nr = (size_t)n_rows;
-    auto cleanup = [&]() { dev_free(c, &d_key, ns); dev_free(c, &d_primer, ns); dev_free(c, &d_rkey, nr); dev_free(c, &d_roff, nr + 1); };
-    int rc;
-    if ((rc = dev_alloc(c, &d_key, ns)) || (rc = dev_alloc(c, &d_primer, ns)) || (rc = dev_alloc(c, &d_rkey, nr)) || (rc = dev_alloc(c, &d_roff, nr + 1))) {
-        cleanup(); return rc;
-    }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_key, key.data(), sizeof(long long) * ns, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_primer, primer.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rkey, row_key.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    rc = e == hipSuccess ? join_device(c, d_key, d_primer, n_sites, d_roff, n_rows, n_bases, d_rkey, size_lo, size_hi)
-                         : fail(c, MP_ERR_DEVICE, "mp_amplicon_join: %s", hipGetErrorString(e));
-    if (rc == MP_OK) {
-        e = hipEventRecord(ev[1], c->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        c->ot_ms[2] = ms;
-        if (e != hipSuccess) rc = fail(c, MP_ERR_DEVICE, "mp_amplicon_join: %s", hipGetErrorString(e));
-    }
+    DevBuf<long long> d_key(c);
+    DevBuf<int32_t> d_primer(c);
+    if ((rc = d_key.alloc((size_t)n_sites)) || (rc = d_primer.alloc((size_t)n_sites))) return rc;
+    HIPCK_WAIT(c, d_key.upload(key.data(), key.size()));
+    HIPCK_WAIT(c, d_primer.upload(primer.data(), primer.size()));
+    HIPCK_WAIT(c, R.upload());
+    StageClock join;                         // the join alone, on the device's clock
+    join.begin(c);
+    rc = join_device(c, d_key.p, d_primer.p, n_sites, R.d_roff.p, R.n_rows, R.n_bases, R.d_rkey.p, size_lo, size_hi);
+    if (rc == MP_OK) join.end(c);
     (void)hipStreamSynchronize(c->stream);               // (the host arrays above leave scope)
-    for (auto &x : ev) if (x) (void)hipEventDestroy(x);
-    cleanup();
+    join.read(c->ot_ms + 2);
     if (rc == MP_OK) rc = copy_out(c, cap, out, n_out);
     // what the join made stays only for this call's copy: it belongs to no store
-    dev_free(c, &c->ot_out, (size_t)c->ot_n * 6);
-    c->ot_n = 0;
+    drop_products(c);
     c->ot_ms[3] = ms_since(t0);
     return rc;
 }

@@ -46,77 +46,34 @@ __global__ __launch_bounds__(kBlock) void seq_pack_kernel(const uint8_t *__restr
     }
 }
 
-// the scan itself on device text (bytes of this call, or the resident store when `code` is set); max_gap > 0: the gapped rule of
-// mprime_offtarget.h on the resident store with the penalty ceiling `pen` (kmm_gap_kernel), else max_mm mismatches (kmm_kernel)
-int kmm_scan_device(mp_ctx *c, const uint8_t *d_bytes, const int64_t *d_roff, const unsigned long long *code, const unsigned long long *flag,
-                    const int64_t *d_woff, const int64_t *roff_host, int32_t n_rows, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off,
-                    int32_t max_mm, int32_t term, int64_t cap, int32_t *hits, int64_t *n_hits, int32_t pen = 0, int32_t max_gap = 0) {
-    int longest = 0;
-    for (int32_t i = 0; i < n_pat; i++) {
-        const int len = pat_off[i + 1] - pat_off[i];
-        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
-        for (int j = 0; j < len; j++) {
-            const uint8_t m = pat_codes[pat_off[i] + j];
-            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
-        }
-        longest = std::max(longest, len);
-    }
-    const bool two_words = longest > 32;             // one pattern longer than 32 bases: the two-word kernel for the whole call
-    std::vector<KmmPat<1>> pats1;
-    std::vector<KmmPat<2>> pats2;
-    if (two_words) kmm_patterns<2>(n_pat, pat_codes, pat_off, term, pats2);
-    else kmm_patterns<1>(n_pat, pat_codes, pat_off, term, pats1);
-    const size_t n_entries = two_words ? pats2.size() : pats1.size();
-    const size_t pat_bytes = two_words ? sizeof(KmmPat<2>) * pats2.size() : sizeof(KmmPat<1>) * pats1.size();
-    const void *pat_src = two_words ? (const void *)pats2.data() : (const void *)pats1.data();
-    std::vector<int32_t> blk_row, blk_seg;
-    for (int32_t r = 0; r < n_rows; r++) {
-        const int64_t len = roff_host[r + 1] - roff_host[r];
-        if (len < 0 || len > 0x7fffffffLL) return fail(c, MP_ERR_ARG, "sequence %d has bad length", r);
-        for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
-    }
-    if (blk_row.empty()) return MP_OK;
-    const size_t nb = blk_row.size();
-    int32_t *d_brow = nullptr, *d_bseg = nullptr, *d_hits = nullptr;
-    uint8_t *d_pats = nullptr;
-    unsigned long long *d_n = nullptr;
-    const size_t hcap = (size_t)std::max<int64_t>(cap, 1) * 4;
-    int rc = MP_OK;
-    auto cleanup = [&]() {
-        dev_free(c, &d_brow, nb); dev_free(c, &d_bseg, nb); dev_free(c, &d_hits, hcap); dev_free(c, &d_pats, pat_bytes); dev_free(c, &d_n, 1);
-    };
-    hipError_t e = hipSuccess;
-    if ((rc = dev_alloc(c, &d_brow, nb)) || (rc = dev_alloc(c, &d_bseg, nb)) || (rc = dev_alloc(c, &d_hits, hcap)) ||
-        (rc = dev_alloc(c, &d_pats, pat_bytes)) || (rc = dev_alloc(c, &d_n, 1))) { cleanup(); return rc; }
-    if (e == hipSuccess) e = hipMemcpyAsync(d_brow, blk_row.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bseg, blk_seg.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pats, pat_src, pat_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) {
-#define MP_KMM_LAUNCH(NW, RES)                                                                                                               \
-    hipLaunchKernelGGL((kmm_kernel<NW, RES, KmmAppend>), dim3((unsigned)nb), dim3(kBlock), 0, c->stream, d_bytes, d_roff, code, flag, d_woff, \
-                       d_brow, d_bseg, reinterpret_cast<const KmmPat<NW> *>(d_pats), (int)n_entries, (int)max_mm, KmmAppend{(long long)cap, d_hits, d_n})
-#define MP_KMM_GAP_LAUNCH(NW)                                                                                                                 \
-    hipLaunchKernelGGL((kmm_gap_kernel<NW, KmmAppend>), dim3((unsigned)nb), dim3(kBlock), 0, c->stream, d_roff, code, flag, d_woff, d_brow, d_bseg, \
-                       reinterpret_cast<const KmmPat<NW> *>(d_pats), (int)n_entries, (int)pen, (int)max_gap, (int)term,                         \
-                       KmmAppend{(long long)cap, d_hits, d_n})
-        if (code && max_gap > 0) { if (two_words) MP_KMM_GAP_LAUNCH(2); else MP_KMM_GAP_LAUNCH(1); }
-        else if (code) { if (two_words) MP_KMM_LAUNCH(2, true); else MP_KMM_LAUNCH(1, true); }
-        else { if (two_words) MP_KMM_LAUNCH(2, false); else MP_KMM_LAUNCH(1, false); }
-#undef MP_KMM_LAUNCH
-#undef MP_KMM_GAP_LAUNCH
-        e = hipGetLastError();
-    }
+// the scan itself on device text X (the bytes of this call, or the resident store); max_gap >= 0: the gapped rule of mprime_offtarget.h
+// with the penalty ceiling `budget`, else `budget` mismatches (kmm_tables)
+int kmm_scan_device(mp_ctx *c, const KmmText &X, const int64_t *roff_host, int32_t n_rows, int32_t n_pat, const uint8_t *pat_codes,
+                    const int32_t *pat_off, int32_t budget, int32_t max_gap, int32_t term, int64_t cap, int32_t *hits, int64_t *n_hits) {
+    int rc;
+    if ((rc = kmm_check_patterns(c, n_pat, pat_codes, pat_off))) return rc;
+    std::vector<int32_t> all((size_t)n_pat);                              // one budget: every pattern in one table
+    std::iota(all.begin(), all.end(), 0);
+    const KmmTable T = kmm_budget(kmm_table(all, pat_codes, pat_off, nullptr, term), budget, max_gap);
+    KmmBlocks B(c);
+    if ((rc = B.build(roff_host, n_rows))) return rc;
+    if (B.size() == 0) return MP_OK;
+    DevBuf<int32_t> d_hits(c);
+    DevBuf<uint8_t> d_pats(c);
+    DevBuf<unsigned long long> d_n(c);
+    if ((rc = d_hits.alloc((size_t)std::max<int64_t>(cap, 1) * 4)) || (rc = d_pats.alloc(T.bytes.size())) || (rc = d_n.alloc(1))) return rc;
+    HIPCK_WAIT(c, B.upload());
+    HIPCK_WAIT(c, d_pats.upload(T.bytes.data(), T.bytes.size()));
+    HIPCK_WAIT(c, d_n.zero());
+    HIPCK_WAIT(c, (kmm_launch<kKmmBytes | kKmmGaps>(c, X, B, T, d_pats.p, term, KmmAppend{(long long)cap, d_hits.p, d_n.p})));
     unsigned long long n = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && cap) {
-        const size_t got = (size_t)std::min<unsigned long long>(n, (unsigned long long)cap);
-        if (got) e = hipMemcpyAsync(hits, d_hits, sizeof(int32_t) * 4 * got, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCK_WAIT(c, hipMemcpyAsync(&n, d_n.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));              // (the block list and the table may go now)
+    const size_t got = cap ? (size_t)std::min<unsigned long long>(n, (unsigned long long)cap) : 0;
+    if (got) {
+        HIPCK_WAIT(c, hipMemcpyAsync(hits, d_hits.p, sizeof(int32_t) * 4 * got, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
     }
-    cleanup();
-    if (e != hipSuccess) return fail(c, MP_ERR_DEVICE, "mp_kmm_scan: %s", hipGetErrorString(e));
     *n_hits = (int64_t)n;
     return MP_OK;
 }
@@ -201,19 +158,15 @@ int mp_kmm_scan(mp_ctx *c, const uint8_t *bytes, const int64_t *row_off, int32_t
     const size_t total = (size_t)(row_off[n_rows] - row_off[0]);
     std::vector<int64_t> roff((size_t)n_rows + 1);
     for (int32_t r = 0; r <= n_rows; r++) roff[(size_t)r] = row_off[r] - row_off[0];
-    uint8_t *d_bytes = nullptr;
-    int64_t *d_roff = nullptr;
+    DevBuf<uint8_t> d_bytes(c);
+    DevBuf<int64_t> d_roff(c);
     int rc;
-    if ((rc = dev_alloc(c, &d_bytes, total + 16)) || (rc = dev_alloc(c, &d_roff, (size_t)n_rows + 1))) {
-        dev_free(c, &d_bytes, total + 16); dev_free(c, &d_roff, (size_t)n_rows + 1);
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(d_bytes, bytes + row_off[0], total, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * roff.size(), hipMemcpyHostToDevice, c->stream);
-    rc = e == hipSuccess ? kmm_scan_device(c, d_bytes, d_roff, nullptr, nullptr, nullptr, roff.data(), n_rows, n_pat, pat_codes, pat_off, max_mm, term, cap, hits, n_hits)
-                         : fail(c, MP_ERR_DEVICE, "mp_kmm_scan: %s", hipGetErrorString(e));
-    (void)hipStreamSynchronize(c->stream);
-    dev_free(c, &d_bytes, total + 16); dev_free(c, &d_roff, (size_t)n_rows + 1);
+    if ((rc = d_bytes.alloc(total + 16)) || (rc = d_roff.alloc((size_t)n_rows + 1))) return rc;
+    HIPCK_WAIT(c, d_bytes.upload(bytes + row_off[0], total));
+    HIPCK_WAIT(c, d_roff.upload(roff.data(), roff.size()));
+    rc = kmm_scan_device(c, KmmText{d_bytes.p, d_roff.p, nullptr, nullptr, nullptr}, roff.data(), n_rows, n_pat, pat_codes, pat_off, max_mm, -1, term,
+                         cap, hits, n_hits);
+    (void)hipStreamSynchronize(c->stream);                  // (roff leaves scope)
     return rc;
 }
 
@@ -225,8 +178,7 @@ int mp_kmm_scan_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, con
     HIPCK(c, hipSetDevice(c->dev));
     *n_hits = 0;
     if (c->sq_n == 0 || n_pat == 0) return MP_OK;
-    return kmm_scan_device(c, c->sq_bytes, c->sq_roff, c->sq_code, c->sq_flag, c->sq_woff, c->sq_roff_host.data(), c->sq_n, n_pat, pat_codes, pat_off,
-                           max_mm, term, cap, hits, n_hits);
+    return kmm_scan_device(c, kmm_store(c), c->sq_roff_host.data(), c->sq_n, n_pat, pat_codes, pat_off, max_mm, -1, term, cap, hits, n_hits);
 }
 
 int mp_kmm_gap_scan_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, int32_t max_pen, int32_t max_gap,
@@ -238,10 +190,8 @@ int mp_kmm_gap_scan_resident(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes,
     HIPCK(c, hipSetDevice(c->dev));
     *n_hits = 0;
     if (c->sq_n == 0 || n_pat == 0) return MP_OK;
-    // no gap fits under the ceiling (5 + 3 g > max_penalty), or none is asked for: the ungapped kernel, exactly
-    const int32_t gaps = max_pen >= 8 ? std::min<int32_t>(max_gap, (max_pen - 5) / 3) : 0;
-    return kmm_scan_device(c, c->sq_bytes, c->sq_roff, c->sq_code, c->sq_flag, c->sq_woff, c->sq_roff_host.data(), c->sq_n, n_pat, pat_codes, pat_off,
-                           max_pen / 6, term, cap, hits, n_hits, max_pen, gaps);
+    // (no gap fits under the ceiling, 5 + 3 g > max_penalty, or none is asked for: the ungapped kernel, exactly)
+    return kmm_scan_device(c, kmm_store(c), c->sq_roff_host.data(), c->sq_n, n_pat, pat_codes, pat_off, max_pen, max_gap, term, cap, hits, n_hits);
 }
 
 }  // extern "C"

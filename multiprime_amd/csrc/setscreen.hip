@@ -35,8 +35,7 @@ struct SetScreen {
     size_t cap = 0, headroom = 0;
     long long n = 0;                      // records held
     unsigned long long *d_n = nullptr;
-    int32_t *d_brow = nullptr, *d_bseg = nullptr;
-    size_t nb = 0;                        // workgroups of the scan: (row, segment)
+    KmmBlocks blocks;                     // workgroups of the scan, built when the screen is opened
     SsTable table;
     int32_t next_primer = 0;
     std::vector<int64_t> fwd, rev;        // sites per primer id
@@ -44,6 +43,7 @@ struct SetScreen {
     std::vector<int64_t> last_out;        // the triples of the last add, and the arguments that made them
     std::vector<uint8_t> last_key;
     int64_t adds = 0;
+    explicit SetScreen(mp_ctx *c) : blocks(c) {}
 };
 
 }  // namespace mp
@@ -214,8 +214,6 @@ __global__ __launch_bounds__(kBlock) void ss_site_count_kernel(const SsSite *__r
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
-inline unsigned grid(long long n, long long per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
-
 long long env_count(const char *name, long long dflt) {
     if (const char *v = getenv(name)) { const long long x = atoll(v); if (x > 0) return x; }
     return dflt;
@@ -226,36 +224,6 @@ size_t pow2_ceil(unsigned long long x) {
     while (p < x && p < ((size_t)1 << 40)) p <<= 1;
     return p;
 }
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
-template <class T> struct DevBuf {          // a device block released with its scope (the pool orders a released block on the stream)
-    mp_ctx *c;
-    T *p = nullptr;
-    size_t n = 0;
-    explicit DevBuf(mp_ctx *ctx) : c(ctx) {}
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    int alloc(size_t k) { n = k ? k : 1; return dev_alloc(c, &p, n); }
-    ~DevBuf() { dev_free(c, &p, n); }
-};
-
-struct StageClock {                          // device time of one stage on the context's stream, added to *ms when it is read
-    hipEvent_t a = nullptr, b = nullptr;
-    void begin(mp_ctx *c) {
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, c->stream) != hipSuccess) drop();
-    }
-    void end(mp_ctx *c) { if (a && b && hipEventRecord(b, c->stream) != hipSuccess) drop(); }
-    void read(double *ms) {                  // after the stream was synchronised
-        float x = 0;
-        if (a && b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&x, a, b) == hipSuccess) *ms += x;
-        drop();
-    }
-    void drop() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); a = b = nullptr; (void)hipGetLastError(); }
-    ~StageClock() { drop(); }
-};
 
 void table_free(mp_ctx *c, SsTable &T) {
     dev_free(c, &T.key, T.slots); dev_free(c, &T.cnt, T.slots); dev_free(c, &T.flags, 3);
@@ -295,7 +263,7 @@ int join_side(mp_ctx *c, const SsSite *sites, const JoinSide &J, const int64_t *
     if ((rc = cnt.alloc((size_t)n_bins)) || (rc = start.alloc((size_t)n_bins + 1)) || (rc = r_off.alloc((size_t)n_r)) || (rc = r_primer.alloc((size_t)n_r))) return rc;
     StageClock bin, join;
     bin.begin(c);
-    HIPCK(c, hipMemsetAsync(cnt.p, 0, sizeof(unsigned) * (size_t)n_bins, c->stream));
+    HIPCK(c, cnt.zero());
     hipLaunchKernelGGL(ss_bin_count_kernel, dim3(grid(n_r, kBlock)), dim3(kBlock), 0, c->stream, sites, J.r0, J.r1, shift, n_bins, cnt.p);
     hipLaunchKernelGGL(ss_bin_scan_kernel, dim3(1), dim3(kBlock), 0, c->stream, cnt.p, n_bins, start.p);
     hipLaunchKernelGGL(ss_bin_scatter_kernel, dim3(grid(n_r, kBlock)), dim3(kBlock), 0, c->stream, sites, J.r0, J.r1, shift, n_bins, cnt.p, n_r, r_off.p,
@@ -354,13 +322,9 @@ int copy_triples(const std::vector<int64_t> &all, int64_t cap, int64_t *out, int
     return MP_OK;
 }
 
-template <class T> void put(std::vector<uint8_t> &k, const T *p, size_t n) {
-    const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
-    k.insert(k.end(), b, b + sizeof(T) * n);
-}
-
 void release_device(mp_ctx *c, SetScreen *S) {
-    dev_free(c, &S->sites, S->cap); dev_free(c, &S->d_n, 1); dev_free(c, &S->d_brow, S->nb); dev_free(c, &S->d_bseg, S->nb);
+    dev_free(c, &S->sites, S->cap); dev_free(c, &S->d_n, 1);
+    S->blocks.release();
     table_free(c, S->table);
     S->cap = 0;
 }
@@ -368,53 +332,36 @@ void release_device(mp_ctx *c, SetScreen *S) {
 // the list with room for `want` records, the first S->n of them kept
 int list_reserve(mp_ctx *c, SetScreen *S, size_t want) {
     if (want <= S->cap) return MP_OK;
-    SsSite *nl = nullptr;
+    DevBuf<SsSite> nl(c);
     int rc;
-    if ((rc = dev_alloc(c, &nl, want))) return rc;
-    hipError_t e = hipSuccess;
-    if (S->n) e = hipMemcpyAsync(nl, S->sites, sizeof(SsSite) * (size_t)S->n, hipMemcpyDeviceToDevice, c->stream);
-    if (e != hipSuccess) { dev_free(c, &nl, want); return fail(c, MP_ERR_DEVICE, "set screen list: %s", hipGetErrorString(e)); }
-    dev_free(c, &S->sites, S->cap);
-    S->sites = nl;
-    S->cap = want;
+    if ((rc = nl.alloc(want))) return rc;
+    if (S->n) HIPCK(c, hipMemcpyAsync(nl.p, S->sites, sizeof(SsSite) * (size_t)S->n, hipMemcpyDeviceToDevice, c->stream));
+    std::swap(nl.p, S->sites);                          // (the old list goes with nl)
+    std::swap(nl.n, S->cap);
     return MP_OK;
 }
 
-// the scan of the new reads into the list from S->n on; *n_total = the records the list must hold
-template <int NW>
-int scan_table(mp_ctx *c, SetScreen *S, const std::vector<KmmPat<NW>> &pats) {
-    if (pats.empty() || S->nb == 0) return MP_OK;
-    DevBuf<KmmPat<NW>> d_pats(c);
+// the scan of one table of new reads into the list from *S->d_n on
+int scan_table(mp_ctx *c, SetScreen *S, const KmmTable &T) {
+    if (T.n == 0 || S->blocks.size() == 0) return MP_OK;
+    DevBuf<uint8_t> d_pats(c);
     int rc;
-    if ((rc = d_pats.alloc(pats.size()))) return rc;
-    HIPCK(c, hipMemcpyAsync(d_pats.p, pats.data(), sizeof(KmmPat<NW>) * pats.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL((kmm_kernel<NW, true, SsAppend>), dim3((unsigned)S->nb), dim3(kBlock), 0, c->stream, (const uint8_t *)c->sq_bytes,
-                       (const int64_t *)c->sq_roff, (const unsigned long long *)c->sq_code, (const unsigned long long *)c->sq_flag,
-                       (const int64_t *)c->sq_woff, (const int32_t *)S->d_brow, (const int32_t *)S->d_bseg, (const KmmPat<NW> *)d_pats.p,
-                       (int)pats.size(), (int)S->mm, SsAppend{S->sites, (long long)S->cap, S->d_n, c->sq_roff});
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipStreamSynchronize(c->stream));          // (the table leaves scope)
+    if ((rc = d_pats.alloc(T.bytes.size()))) return rc;
+    HIPCK(c, d_pats.upload(T.bytes.data(), T.bytes.size()));
+    HIPCK(c, kmm_launch<0>(c, kmm_store(c), S->blocks, T, d_pats.p, S->term, SsAppend{S->sites, (long long)S->cap, S->d_n, c->sq_roff}));
+    HIPCK(c, hipStreamSynchronize(c->stream));          // (the device table leaves scope)
     return MP_OK;
 }
 
 int add_run(mp_ctx *c, SetScreen *S, int32_t n_pat, const uint8_t *pat_codes, const int32_t *pat_off, const int32_t *read_primer,
             double *ms, int64_t *counts) {
     // one table per kernel form: the reads of a primer have one length, so a primer is whole in one of them
-    std::vector<KmmPat<1>> p1;
-    std::vector<KmmPat<2>> p2;
+    KmmTable tables[2];
     for (int form = 0; form < 2; form++) {
-        std::vector<uint8_t> codes;
-        std::vector<int32_t> off{0}, ids;
-        for (int32_t i = 0; i < n_pat; i++) {
-            const int len = pat_off[i + 1] - pat_off[i];
-            if ((len > 32) != (form == 1)) continue;
-            codes.insert(codes.end(), pat_codes + pat_off[i], pat_codes + pat_off[i + 1]);
-            off.push_back((int32_t)codes.size());
-            ids.push_back(read_primer[i]);
-        }
-        if (ids.empty()) continue;
-        if (form == 0) { kmm_patterns<1>((int32_t)ids.size(), codes.data(), off.data(), S->term, p1); for (auto &P : p1) P.id = ids[(size_t)P.id]; }
-        else { kmm_patterns<2>((int32_t)ids.size(), codes.data(), off.data(), S->term, p2); for (auto &P : p2) P.id = ids[(size_t)P.id]; }
+        std::vector<int32_t> idx;
+        for (int32_t i = 0; i < n_pat; i++) if ((pat_off[i + 1] - pat_off[i] > 32) == (form == 1)) idx.push_back(i);
+        tables[form] = kmm_table(idx, pat_codes, pat_off, read_primer, S->term);
+        tables[form].budget = S->mm;
     }
     const long long n_old = S->n;
     int rc;
@@ -426,9 +373,9 @@ int add_run(mp_ctx *c, SetScreen *S, int32_t n_pat, const uint8_t *pat_codes, co
         HIPCK(c, hipStreamSynchronize(c->stream));
         StageClock scan;
         scan.begin(c);
-        if ((rc = scan_table<1>(c, S, p1)) || (rc = scan_table<2>(c, S, p2))) return rc;
+        if ((rc = scan_table(c, S, tables[0])) || (rc = scan_table(c, S, tables[1]))) return rc;
         scan.end(c);
-        counts[0] += (p1.empty() ? 0 : 1) + (p2.empty() ? 0 : 1);
+        counts[0] += (tables[0].n ? 1 : 0) + (tables[1].n ? 1 : 0);
         HIPCK(c, hipMemcpyAsync(&n_total, S->d_n, sizeof n_total, hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipStreamSynchronize(c->stream));
         scan.read(ms);
@@ -444,7 +391,7 @@ int add_run(mp_ctx *c, SetScreen *S, int32_t n_pat, const uint8_t *pat_codes, co
     if (S->n > n_old) {
         DevBuf<unsigned long long> d_cnt(c);
         if ((rc = d_cnt.alloc(2 * (size_t)n_p))) return rc;
-        HIPCK(c, hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long) * 2 * (size_t)n_p, c->stream));
+        HIPCK(c, d_cnt.zero());
         hipLaunchKernelGGL(ss_site_count_kernel, dim3(grid(S->n - n_old, kBlock)), dim3(kBlock), 0, c->stream, (const SsSite *)S->sites, n_old, S->n,
                            (int)first, (int)n_p, d_cnt.p);
         HIPCK(c, hipGetLastError());
@@ -487,26 +434,18 @@ int mp_setscreen_begin(mp_ctx *c, int32_t size_lo, int32_t size_hi, int32_t max_
     if (c->ss) return fail(c, MP_ERR_ARG, "mp_setscreen_begin: a set screen is open already (mp_setscreen_end closes it)");
     if (c->sq_n == 0) return fail(c, MP_ERR_ARG, "mp_setscreen_begin: no sequence store (mp_seq_load comes first)");
     HIPCK(c, hipSetDevice(c->dev));
-    SetScreen *S = new SetScreen;
+    SetScreen *S = new SetScreen(c);
     S->lo = size_lo; S->hi = size_hi; S->mm = max_mm; S->term = term;
     S->headroom = (size_t)env_count("MP_SETSCREEN_SITES", 1 << 20);
-    std::vector<int32_t> blk_row, blk_seg;
-    for (int32_t r = 0; r < c->sq_n; r++) {
-        const int64_t len = c->sq_roff_host[(size_t)r + 1] - c->sq_roff_host[(size_t)r];
-        for (int64_t sgm = 0; sgm * kSeg < len; sgm++) { blk_row.push_back(r); blk_seg.push_back((int32_t)sgm); }
-    }
-    S->nb = blk_row.size();
     int rc;
-    if ((rc = dev_alloc(c, &S->d_n, 1)) || (rc = dev_alloc(c, &S->d_brow, S->nb)) || (rc = dev_alloc(c, &S->d_bseg, S->nb)) ||
+    if ((rc = dev_alloc(c, &S->d_n, 1)) || (rc = S->blocks.build(c->sq_roff_host.data(), c->sq_n)) ||
         (rc = table_alloc(c, S->table, pow2_ceil((unsigned long long)env_count("MP_SETSCREEN_TABLE", 1 << 16))))) {
         release_device(c, S); delete S; return rc;
     }
-    hipError_t e = hipSuccess;
-    if (S->nb) {
-        e = hipMemcpyAsync(S->d_brow, blk_row.data(), sizeof(int32_t) * S->nb, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(S->d_bseg, blk_seg.data(), sizeof(int32_t) * S->nb, hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipError_t e = S->blocks.upload();
+    const hipError_t waited = hipStreamSynchronize(c->stream);
+    S->blocks.drop_host();
+    if (e == hipSuccess) e = waited;
     if (e != hipSuccess) { release_device(c, S); delete S; return fail(c, MP_ERR_DEVICE, "mp_setscreen_begin: %s", hipGetErrorString(e)); }
     for (int i = 0; i < 4; i++) c->ss_ms[i] = 0;
     for (int i = 0; i < 8; i++) c->ss_counts[i] = 0;
@@ -526,17 +465,13 @@ int mp_setscreen_add(mp_ctx *c, int32_t n_pat, const uint8_t *pat_codes, const i
     const auto t0 = std::chrono::steady_clock::now();
     *n_out = 0;
     if (n_pat == 0) return MP_OK;
-    for (int32_t i = 0; i < n_pat; i++) {
-        const int len = pat_off[i + 1] - pat_off[i];
-        if (len < 4 || len > MP_PATTERN_MAX_LEN) return fail(c, MP_ERR_ARG, "pattern %d has length %d (4..%d supported)", i, len, MP_PATTERN_MAX_LEN);
-        for (int j = 0; j < len; j++) {
-            const uint8_t m = pat_codes[pat_off[i] + j];
-            if (m != 1 && m != 2 && m != 4 && m != 8) return fail(c, MP_ERR_ARG, "pattern %d is not a concrete A/C/G/T sequence", i);
-        }
-        if (read_primer[i] < 0 || (i && read_primer[i] < read_primer[i - 1])) return fail(c, MP_ERR_ARG, "mp_setscreen_add: read_primer must be non-negative and non-decreasing (read %d)", i);
-        if (i && read_primer[i] == read_primer[i - 1] && len != pat_off[i] - pat_off[i - 1])
-            return fail(c, MP_ERR_ARG, "mp_setscreen_add: the reads of primer %d differ in length (read %d)", read_primer[i], i);
-    }
+    if (int rc = kmm_check_patterns(c, n_pat, pat_codes, pat_off, [&](int32_t i) {
+            if (read_primer[i] < 0 || (i && read_primer[i] < read_primer[i - 1]))
+                return fail(c, MP_ERR_ARG, "mp_setscreen_add: read_primer must be non-negative and non-decreasing (read %d)", i);
+            if (i && read_primer[i] == read_primer[i - 1] && pat_off[i + 1] - pat_off[i] != pat_off[i] - pat_off[i - 1])
+                return fail(c, MP_ERR_ARG, "mp_setscreen_add: the reads of primer %d differ in length (read %d)", read_primer[i], i);
+            return (int)MP_OK;
+        })) return rc;
     std::vector<uint8_t> key;
     put(key, &n_pat, 1);
     put(key, pat_off, (size_t)n_pat + 1);

@@ -226,10 +226,6 @@ __global__ __launch_bounds__(256) void star_count_kernel(const uint8_t *__restri
     }
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the arrays of one round (kept after it for mp_star_rows / mp_star_counts)
 void free_round(mp_ctx *c) {
     const size_t N = (size_t)c->st_n, S = (size_t)c->st_stride;

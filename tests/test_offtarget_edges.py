@@ -330,6 +330,116 @@ def test_class_screen_equals_model(hip_lib):
         ctx.close()
 
 
+NOWHERE = "ACGTTGCATGCATCGATCGATTAGCACGTTGCA"     # 32 bases that no store of the cases holds: at budget 0 a call without a site
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["a1", "b", "d257"])
+def test_device_bytes_balance(hip_lib, name):
+    """mp_device_bytes around every entry that drives the store scan.  What a call leaves on the device is a function of that call
+    alone: the store, plus the products an off-target screen keeps for its repeat (a call without a site keeps an empty list of one
+    slot).  So the reading after a call is the same every time that call is the last one made, in whatever order the calls ran —
+    for the entries that keep nothing on the device it is the store's; and the two calls that touch no kept state at all (the
+    validation scan, and a call refused for its arguments before anything is dropped) leave the reading exactly as they found it,
+    which is the form the statement takes for them: what an earlier screen kept is still there and still counted."""
+    c = cases.get(name)
+    codes, poff, primer, mm = args_of(c)
+    classes = np.arange(len(c.reads), dtype=np.int32) % 2
+    none = R.encode([NOWHERE])
+    short = R.encode(["ACG"])
+    one = np.zeros(1, np.int32)
+    sites = np.array([[0, 0, 5, 1], [0, 2, 7, 1], [1, 0, 40, 2], [1, 2, 90, 2]], np.int32)
+    csites = np.array([[0, 0, 0, 5, 1], [0, 1, 0, 60, 2], [1, 0, 0, 9, 3], [1, 1, 0, 40, 4], [1, 1, 3, 40, 4]], np.int32)
+    ctx = hip_lib.context(0)
+
+    def refused():
+        with pytest.raises(Exception, match="pattern 0 has length 3"):
+            ctx.offtarget_resident(*short, one, one, c.term, c.lo, c.hi)
+
+    def no_site():
+        assert len(ctx.offtarget_resident(*none, one, one * 0, c.term, c.lo, c.hi)) == 0
+        counts = ctx.offtarget_stats()[1]
+        assert counts["forward_sites"] == counts["reverse_sites"] == 0
+
+    calls = {
+        "offtarget_resident": lambda: ctx.offtarget_resident(codes, poff, primer, mm, c.term, c.lo, c.hi),
+        "offtarget_gap_resident": lambda: ctx.offtarget_gap_resident(codes, poff, primer, 6 * mm + 8, 1, c.term, c.lo, c.hi),
+        "offtarget_classes": lambda: ctx.offtarget_classes(codes, poff, primer, classes, mm, c.term, c.lo, c.hi),
+        "amplicon_join": lambda: ctx.amplicon_join(sites, 20, 100),
+        "amplicon_join_classes": lambda: ctx.amplicon_join_classes(csites, 20, 100),
+        "kmm_scan_resident": lambda: ctx.kmm_scan_resident(codes, poff, int(max(c.budgets)), c.term),
+        "zero_patterns": lambda: ctx.offtarget_resident(np.zeros(1, np.uint8), np.zeros(1, np.int32), one[:0], one[:0], c.term, c.lo, c.hi),
+        "no_site": no_site,
+        "refused": refused,
+    }
+    untouched = {"kmm_scan_resident", "refused"}                     # no kept state read or written
+    store_only = {"offtarget_classes", "amplicon_join", "amplicon_join_classes", "zero_patterns"}
+    order = list(calls)
+    rng = np.random.default_rng(5)
+    # every call after every other one at least once: the list, its reverse, each call twice in a row (the repeat is served from
+    # what the first kept), and two shuffles
+    runs = [order, order[::-1], [n for n in order for _ in (0, 1)], list(rng.permutation(order)), list(rng.permutation(order))]
+    seen = {n: set() for n in calls}
+    try:
+        before = ctx.device_bytes()
+        ctx.seq_load(*encode_store(c.seqs))
+        store = ctx.device_bytes()
+        assert store - before == ctx.seq_info()[2] > 0
+        last = store
+        for run in runs:
+            for n in run:
+                calls[n]()
+                now = ctx.device_bytes()
+                if n in untouched:
+                    assert now == last, (n, now, last)
+                else:
+                    seen[n].add(now)
+                last = now
+        assert all(len(seen[n]) == 1 for n in calls if n not in untouched), seen
+        assert all(seen[n] == {store} for n in store_only), (seen, store)
+        assert seen["no_site"] == {store + 6 * 4}                     # the empty list's one slot
+        assert min(seen["offtarget_resident"]) > store and min(seen["offtarget_gap_resident"]) > store     # products are kept
+        ctx.seq_free()
+        assert ctx.device_bytes() == before
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_device_bytes_balance_of_the_set_screen(hip_lib, monkeypatch):
+    """begin -> adds -> end returns to the reading before begin, with a list of one record of headroom and a pair table of one slot:
+    both are regrown during the adds."""
+    monkeypatch.setenv("MP_SETSCREEN_SITES", "1")
+    monkeypatch.setenv("MP_SETSCREEN_TABLE", "1")
+    c = cases.get("a1")
+    reads = sorted(c.reads, key=len)                                  # the 4-base read and the palindrome first: sites everywhere
+    ctx = hip_lib.context(0)
+    try:
+        before = ctx.device_bytes()
+        ctx.seq_load(*encode_store(c.seqs))
+        store = ctx.device_bytes()
+        for _ in (0, 1):
+            ctx.setscreen_begin(c.lo, c.hi, 1, 0)
+            regrows = np.zeros(2, np.int64)
+            for first in (0, 2, 4):
+                batch = reads[first:first + 2]
+                ctx.setscreen_add(*R.encode(batch), np.arange(first, first + len(batch), dtype=np.int32))
+                counts = ctx.setscreen_stats()[1]
+                regrows += (counts["list_regrows"], counts["table_regrows"])
+            assert (regrows > 0).all(), regrows
+            assert ctx.device_bytes() > store
+            ctx.setscreen_end()
+            assert ctx.device_bytes() == store
+        ctx.setscreen_begin(c.lo, c.hi, 1, 0)                          # the store goes under an open screen: its device side goes too
+        ctx.setscreen_add(*R.encode(reads[:2]), np.arange(2, dtype=np.int32))
+        ctx.seq_free()
+        assert ctx.device_bytes() == before
+        ctx.setscreen_end()
+        assert ctx.device_bytes() == before
+    finally:
+        ctx.close()
+
+
 @pytest.mark.gpu
 def test_kept_products(hip_lib):
     a, b = cases.get("a1"), cases.get("b")
