@@ -137,6 +137,12 @@ int mp_plan_chain(const mp_plan *p, int32_t w, int32_t seed, int32_t cap, uint8_
  * (V20:846).  Fails with MP_ERR_ARG if a candidate's perfect coverage differs from the host's running sum
  * (the two are the same quantity). */
 int mp_plan_finish(mp_plan *p, const int64_t *ev);
+/* The same end for final primers GIVEN by the caller (the multiPrime2 selection of mprime_subset.h) instead of replayed from the chains:
+ * primer_codes [n_planned][k] (IUPAC symbol codes, no gaps) and ev [n_planned][3] = mp_eval_candidates of exactly those primers, in the
+ * order of the planned windows.  Perfect coverage is the sum of `cover` over the primer's expansions (MP_ERR_ARG if the evaluation counted
+ * something else), F / R mis-coverage = perfect + ev[1] / ev[2], nonsense_primer_number = the expansions that are no key of `cover`
+ * (V2:1215: no phantom key here).  mp_plan_results then returns these.  Primers of at most 32 bases. */
+int mp_plan_finish_given(mp_plan *p, const uint8_t *primer_codes, const int64_t *ev);
 /* per planned window, ascending: window index, entropies (rounded as the reference prints them), the chosen primer's
  * symbol codes [n][k], its perfect coverage, F / R mis-coverage (perfect + admissible), nonsense_primer_number,
  * number of degenerate positions, cover_number */

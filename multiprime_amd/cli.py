@@ -22,6 +22,9 @@ Extra, optional flags (additions must stay optional):
                  pair and one JSON summary (clusters per second) at the end.  --batch-workers T: clusters in flight per GPU
                  (threads with a context each; default up to 8): a small cluster is host-bound, several of them overlap.
                  --batch-procs P: P processes per GPU share its clusters (the per-cluster Python does not scale over threads).
+  -m METHOD      multiPrime1 (default: the nearest-neighbour chain of V20) or multiPrime2: the global-optimum selection of the
+                 reference's multiPrime2-core_V2.py (-m multiPrime2) as a GPU subset search (multiprime_amd/subset.py); everything
+                 around the selection stays V20.  One GPU, -l <= 32; INTEGRATION.md §2.
 """
 from __future__ import annotations
 
@@ -54,6 +57,9 @@ def parse_args(argv=None):
                    help="Accepted for compatibility (the reference's process pool is inert; the work runs on the GPU).")
     p.add_argument("-a", "--away", type=int, default=4, metavar="<int>", help="Hairpin: minimal distance of paired bases. Default: 4.")
     p.add_argument("-o", "--out", type=str, default=None, metavar="<file>", help="output file")
+    p.add_argument("-m", "--method", type=str, default="multiPrime1", choices=("multiPrime1", "multiPrime2"), metavar="<str>",
+                   help="How a window's seed becomes degenerate: multiPrime1 (default), the nearest-neighbour chain; multiPrime2, the "
+                        "global optimum over all subsets of -n - 1 substitutions (multiPrime2-core_V2.py; one GPU, -l at most 32).")
     p.add_argument("--device", type=int, default=None, help="GPU ordinal (default 0); with several ranks: the ordinal of local rank 0, rank r opens D + r")
     p.add_argument("--grid", default=None, metavar="RxG|auto",
                    help="with several ranks: R row shards x G window groups instead of row shards only (R x G = ranks); auto = as many "
@@ -76,6 +82,12 @@ def parse_args(argv=None):
         p.error("the following arguments are required: -i/--input, -o/--out (or --batch)")      # exit code 2, like the reference's parser
     if args.ngpu < 1:
         p.error("--ngpu must be at least 1")
+    if args.method == "multiPrime2":
+        # never a silent fall-back to multiPrime1: what the subset search does not cover is refused by name
+        if args.plen > 32:
+            p.error("-m multiPrime2 takes primers of at most 32 bases (-l {}): a set of substitutions is a 128-bit mask".format(args.plen))
+        if args.ngpu > 1 or args.grid or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("-m multiPrime2 runs on one GPU: not with --ngpu > 1, --grid or several ranks (--batch works)")
     return args
 
 
@@ -108,7 +120,8 @@ def _core(args, inp, out, device, comm, context=None, grid=None):
                          number_of_dege_bases=args.dnum, score_of_dege_bases=args.degeneracy,
                          raw_entropy_threshold=args.entropy, product_len=args.size, position=args.coordinate,
                          variation=args.variation, distance=args.away, GC=args.gc, nproc=args.proc, outfile=out,
-                         device=device, comm=comm, write_json=not args.no_json, write_bitsets=args.bitsets, context=context, grid=grid)
+                         device=device, comm=comm, write_json=not args.no_json, write_bitsets=args.bitsets, context=context, grid=grid,
+                         method=args.method)
 
 
 def _closing_line(e1, e2):

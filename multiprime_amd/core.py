@@ -18,6 +18,10 @@ counts, not on the evaluations — those only decide where to stop — so the ho
 refinement chain of every window and seed, ALL chain members of ALL windows are evaluated in ONE batched launch,
 and the reference's stopping rules are replayed on the results.  Outputs are identical; launches per alignment drop
 from ~12 dependent rounds to one.
+
+method="multiPrime2" (-m multiPrime2 of the reference's multiPrime2-core_V2.py) replaces the chain and its replay by the global-optimum
+selection: the plan supplies statuses, seeds and cover_number, the subsets of substitutions are searched on the device over the histogram
+tables still resident in the context (subset.py, csrc/subset.hip), and one evaluation of the final primers finishes the plan.
 """
 from __future__ import annotations
 
@@ -77,8 +81,19 @@ class NN_degenerate(object):
     def __init__(self, seq_file, primer_length=18, coverage=0.8, number_of_dege_bases=18, score_of_dege_bases=1000,
                  product_len=250, position="2,-1", variation=2, raw_entropy_threshold=3.6, distance=4, GC="0.4,0.6",
                  nproc=10, outfile="", *, library: Library | None = None, device: int = 0, comm=None,
-                 write_json: bool = True, write_bitsets: bool = False, keep_bitsets: bool = False, context=None, grid=None):
+                 write_json: bool = True, write_bitsets: bool = False, keep_bitsets: bool = False, context=None, grid=None,
+                 method: str = "multiPrime1"):
         self.primer_length = int(primer_length)
+        # how a window's seed becomes degenerate: "multiPrime1" = the nearest-neighbour chain (V20), "multiPrime2" = the global optimum over
+        # all subsets of substitutions (multiPrime2-core_V2.py -m multiPrime2: subset.py, csrc/subset.hip); everything around it stays V20
+        if method not in ("multiPrime1", "multiPrime2"):
+            raise ValueError("method must be 'multiPrime1' or 'multiPrime2', not {!r}".format(method))
+        self.method = method
+        if method == "multiPrime2":
+            if comm is not None or grid is not None:
+                raise ValueError("method='multiPrime2' runs on one GPU: not with row shards or window groups")
+            if self.primer_length > 32:
+                raise ValueError("method='multiPrime2' takes primers of at most 32 bases (a set of substitutions is a 128-bit mask)")
         self.coverage = coverage
         self.number_of_dege_bases = number_of_dege_bases
         self.score_of_dege_bases = score_of_dege_bases
@@ -279,6 +294,7 @@ class NN_degenerate(object):
         else:
             ex_w, ex_r, ex_codes, extra = exceptions_on_the_host()
             self._lap("get_exceptions + expand_kmer_words (%d)" % n_ex)
+        self._extra = extra                                  # the IUPAC rows' expansions: entries of the subset search too (method 2)
         if extra is not None:
             self.ctx.set_extra_rows(*extra)
             self._lap("set_extra_rows")
@@ -376,6 +392,26 @@ class NN_degenerate(object):
         flags = self.ctx.dimer_pairs(np.ascontiguousarray(codes, np.uint8).reshape(-1), off, pairs, cached_loss_table(3.0), dg_params(), dg_limit())
         return flags.astype(bool).tolist()
 
+    def _select_by_subsets(self, plan):
+        """Method 2: every planned window's seeds go through the resident subset search (the histogram tables are still in the context,
+        the IUPAC rows' expansions come as extra entries), the step rules are replayed, NM or MM is picked, and ONE evaluation of the final
+        primers finishes the plan — plan.results() then returns what the output stage takes.  Returns that evaluation."""
+        from . import subset
+        N = int(self.number_of_dege_bases)
+        t0 = time.time()
+        wins, s_window, s_seed, s_cover, nm, mm = subset.plan_searches(plan)
+        steps = subset.search_resident(self.ctx, N, s_window, s_seed, s_cover, extra=self._extra)
+        self.stats["subset_search_s"] = time.time() - t0
+        self.stats["subset_searches"] = len(s_window)
+        self.stats["subset_kernel_ms"] = subset.timing(self.ctx).tolist()
+        _, max_count, merged = subset.replay(plan.d, self.primer_length, N, s_seed, s_cover, steps)
+        chosen = subset.choose(plan.d, nm, mm, max_count)
+        final = merged[chosen] if len(chosen) else np.zeros((0, self.primer_length), np.uint8)
+        ev = self.ctx.eval_candidates(wins, final, self._sF, self._sR) if len(wins) else np.zeros((0, 3), np.int64)
+        subset.finish_given(plan, final, ev)
+        self._lap("subset search + replay + eval")
+        return ev
+
     # ------------------------------------------------------------------ driver
     def run(self):
         """V20:1133-1180.  Helper threads of a run (self-dimer launch, coverage bitsets) use the context: whatever way this call ends,
@@ -404,8 +440,11 @@ class NN_degenerate(object):
             self.stats["windows_planned"] = plan.n_planned     # passed the gap / entropy / composition gates (V20:713-740)
             n_cand = plan.n_candidates
             t0 = time.time()
-            cand_w, codes = plan.candidates()
-            if self._win_split:
+            cand_w, codes = plan.candidates() if self.method == "multiPrime1" else (None, None)
+            if self.method == "multiPrime2":
+                ev = self._select_by_subsets(plan)
+                n_cand = plan.n_planned
+            elif self._win_split:
                 # every rank planned its share of the windows: all candidates (rank order = window order) go to everyone, each
                 # rank counts them on its rows, one all-reduce; a rank replays the stopping rules on its own slice
                 mine = len(cand_w)
@@ -429,7 +468,8 @@ class NN_degenerate(object):
             self.stats["n_candidates"] = n_cand
             t0 = time.time()
             self._lap("plan + eval")
-            plan.finish(ev)                      # replay of the stopping rules, NM / MM choice, nonsense counts
+            if self.method == "multiPrime1":
+                plan.finish(ev)                  # replay of the stopping rules, NM / MM choice, nonsense counts
             self._lap("plan.finish")
             res = plan.results()
             if self._win_split:

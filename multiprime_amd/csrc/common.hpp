@@ -348,6 +348,8 @@ struct mp_ctx {
     mp::SetScreen *ss = nullptr;
     double ss_ms[4] = {0, 0, 0, 0};
     int64_t ss_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // global-optimum degenerate positions (subset.hip, include/mprime_subset.h): device times of the last search's three kernels
+    double sub_ms[3] = {0, 0, 0};
     // row-shard collectives (comm.hip): an RCCL communicator (ncclComm_t) when n_ranks > 1
     void *comm = nullptr;
     int n_ranks = 0, rank = 0;               // n_ranks 0: mp_comm_init has not run

@@ -1066,6 +1066,46 @@ int mp_plan_finish(mp_plan *p, const int64_t *ev) {
     return MP_OK;
 }
 
+#if !MP_PLAN_WIDE
+// mp_plan_finish for final primers chosen elsewhere (the multiPrime2 selection, mprime_subset.h: k <= 32, so this unit only)
+int mp_plan_finish_given(mp_plan *p, const uint8_t *primer_codes, const int64_t *ev) {
+    if (!p) return MP_ERR_ARG;
+    if (p->wide) return MP_ERR_ARG;
+    if (!primer_codes || !ev) return pfail(p, MP_ERR_ARG, "mp_plan_finish_given: null argument");
+    const int k = p->P.k;
+    for (size_t pi = 0; pi < p->planned.size(); pi++) {
+        const int32_t w = p->planned[pi];
+        Window &x = p->win[(size_t)w];
+        const uint8_t *codes = primer_codes + pi * (size_t)k;
+        x.primer = Key();
+        x.n_dege = 0;
+        int64_t n_exp = 1;
+        for (int j = 0; j < k; j++) {
+            if (codes[j] == 0 || codes[j] > 15) return pfail(p, MP_ERR_ARG, "mp_plan_finish_given: window %d: symbol code %d at position %d", w, (int)codes[j], j);
+            x.primer.set(j, codes[j]);
+            x.n_dege += set_size(codes[j]) > 1;
+            n_exp *= set_size(codes[j]);
+            if (n_exp > (1 << 22)) return pfail(p, MP_ERR_ARG, "mp_plan_finish_given: window %d: more than 2^22 expansions", w);
+        }
+        int64_t cov = 0;
+        int32_t nonsense = 0;
+        for_each_expansion(codes, k, [&](const Key &e) {
+            const int32_t s = x.cover_map.find(e, x.cover);
+            if (s >= 0) cov += x.cover[(size_t)s].count; else nonsense++;
+        });
+        if (ev[3 * pi] != cov)
+            return pfail(p, MP_ERR_ARG, "perfect-coverage mismatch between the window table and the evaluation at window %d (host %lld, evaluation %lld)",
+                         w, (long long)cov, (long long)ev[3 * pi]);
+        x.cov = cov;
+        x.f_mis = cov + ev[3 * pi + 1];
+        x.r_mis = cov + ev[3 * pi + 2];
+        x.nonsense = nonsense;
+    }
+    p->finished = true;
+    return MP_OK;
+}
+#endif
+
 int mp_plan_results(const mp_plan *p, int32_t *window, double *cbit, double *tbit, uint8_t *primer_codes, int64_t *cov,
                     int64_t *f_mis, int64_t *r_mis, int32_t *nonsense, int32_t *n_dege, int64_t *cover_number) {
     MP_PLAN_FORWARD(mp_plan_results, window, cbit, tbit, primer_codes, cov, f_mis, r_mis, nonsense, n_dege, cover_number);

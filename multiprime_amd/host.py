@@ -46,6 +46,7 @@ HOST_SYMBOLS = [
     ("mp_plan_seeds", C.c_int, [_p, C.c_int32, _p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("mp_plan_chain", C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _p, _p, _p, C.POINTER(C.c_int32)]),
     ("mp_plan_finish", C.c_int, [_p, _p]),
+    ("mp_plan_finish_given", C.c_int, [_p, _p, _p]),
     ("mp_plan_results", C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     ("mp_plan_window_table", C.c_int, [_p, C.c_int32, C.c_int32, C.c_int64, _p, _p, _p, C.POINTER(C.c_int64)]),
     ("mp_plan_write_side_files", C.c_int, [_p, C.c_int32, _p, _p, _p, C.c_uint64, C.c_uint64, _p, _p, C.c_int64, _p, C.c_int32, C.c_int64,
@@ -407,6 +408,14 @@ class Plan:
         if len(ev) != self.n_candidates:
             raise ValueError("one evaluation triple per candidate expected")
         self._ck(self.d.mp_plan_finish(self.h, _ptr(ev) if len(ev) else _ptr(np.zeros(3, np.int64))))
+
+    def finish_given(self, primer_codes: np.ndarray, ev: np.ndarray):
+        """The plan finished with final primers chosen elsewhere (the multiPrime2 selection, subset.py): primer_codes [n_planned][k], ev
+        [n_planned][3] = their evaluation (mp_plan_finish_given); results() then returns them."""
+        primer_codes = np.ascontiguousarray(primer_codes, dtype=np.uint8).reshape(self.n_planned, self.k)
+        ev = np.ascontiguousarray(ev, dtype=np.int64).reshape(self.n_planned, 3)
+        pad = np.zeros(3, np.int64)
+        self._ck(self.d.mp_plan_finish_given(self.h, _ptr(primer_codes if self.n_planned else pad), _ptr(ev if self.n_planned else pad)))
 
     def results(self):
         n = self.n_planned

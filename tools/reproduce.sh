@@ -220,6 +220,12 @@ dege)            # profiles/dege.txt: DegePrime on the recorded 150 x 320 slice 
   timeout -k 10 600 python tools/dege_bench.py 2>&1 | tee $O/dege.txt &&
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof/trace -o t -- python tools/dege_bench.py > /dev/null 2>&1 &&
   python tools/summarize_profile.py $O/prof 2>/dev/null | head -14 | tee -a $O/dege.txt ;;
+subset)          # profiles/subset.txt: the global-optimum selection (-m multiPrime2) on synth 131072 x 1000 and 1048576 x 1000 at -n 4 / -n 6: event times of the three kernels, run() with method 2 beside method 1; a sample of the windows' tables goes to $O/subset_tables.json for the one-core reference timing (tools/subset_bench.py --reference, no GPU)
+  # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
+  set -o pipefail
+  timeout -k 10 300 python -m pytest tests/test_subset_gpu.py -x -q -m gpu 2>&1 | tail -4 | tee $O/pytest.txt &&
+  timeout -k 10 500 python tools/subset_bench.py --rows 131072 --dump $O/subset_tables.json 2>&1 | tee $O/subset.txt &&
+  timeout -k 10 1000 python tools/subset_bench.py --rows 1048576 --repeats 2 2>&1 | tee -a $O/subset.txt ;;
 ont)             # profiles/ont.txt: reads to primers on a synthetic run (200000 reads, 96 primers, about 1000 keys): device ms from mp_ont_stats, run() wall, a one-core difflib loop over 200 reads scaled linearly; then the same run without the pruning bound and on 64-bit masks
   # (pipefail and &&: a failed, faulted or timed-out step ends the target before the next one starts on the same card)
   set -o pipefail
